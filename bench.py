@@ -10,11 +10,17 @@ verdict bitmaps and stake tallies — the only collective the path has (SURVEY.m
 N ranks (``torch.distributed.run``, one process per GPU, 127.0.0.1 rendezvous) from a parent that
 never touches the GPU; under the driver's own ``torch.distributed.run`` it runs as one rank.
 
-Prints ONE JSON line (rank 0):
+A plain run (``python bench.py --gpus 1 --steps N --warmup W``) does only what the headline needs: it
+sets up, warms up, times the N steps, checks the verdicts those steps wrote, writes the last step's
+outputs when ``--dump-outputs DIR`` is given, and prints ONE JSON line (rank 0) with ``value``,
+``ms_per_step`` and
   * ``roofline`` — the dominant kernel, k_verify, timed with HIP events that libnwcrypto records on
     the launch stream around each k_verify launch (nw_profile_*).  ``achieved`` = the kernel's
     algorithmic u32 multiply-accumulates per launch (work model below) / average launch time;
     ``peak`` = the measured v_mad_u64_u32 rate (tools/valu_peak.hip -> profiles/r01_valu_peak.json).
+
+``--full`` adds every other leg to that line (each takes GPU or CPU runs of its own, after the timed
+steps): ``roofline.isolated``, the one-certificate latency, and
   * ``cpu_baseline`` — the oracle's C restatement of dalek 1.0.1 (oracle/nw_ref.c, "port") timed on
     every host core this process may run on, on a bounded sample of the same certificates; the
     per-GPU share of that host (cores / 8 GPUs) is reported beside it.
@@ -26,8 +32,15 @@ Prints ONE JSON line (rank 0):
     every host core.
   * ``msm`` — the variable-base Pippenger path (keys outside the committee cache) at the worker's
     load shape: 64 verify_batch chunks of ~977 signatures over fresh keys.
+  * ``c4`` — the north-star config (configs[3]) timed after the C2 engine is closed, with its own
+    CPU baseline.
+
+``--dump-outputs DIR`` writes what the last timed step computed (ConfigRun.dump_outputs): the arrays
+a caller of nw_verify_certs_dev receives.  The inputs are a function of the arguments alone, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
+import hashlib
 import json
 import math
 import os
@@ -654,6 +667,12 @@ def parse_args(argv):
     ap.add_argument("--validators", type=int, default=None, help="override the config's committee size")
     ap.add_argument("--certs", type=int, default=None, help="override the config's certificate count")
     ap.add_argument("--votes", type=int, default=None, help="override the config's votes per certificate")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other leg (isolated k_verify launches, one-certificate "
+                         "latency, host_fed / msm / worker_digest / latency / digest, the C4 leg, the CPU baselines); "
+                         "the options below that size or disable those legs apply only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--latency-samples", type=int, default=200)
@@ -692,6 +711,10 @@ def parse_args(argv):
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher check without a GPU: ranks meet over gloo, rank 0 prints the world")
     a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1 (the number of timed steps)")
+    if a.warmup < 0:
+        ap.error("--warmup must not be negative")
     if a.hw_queues and not 1 <= a.hw_queues <= 32:
         ap.error("--hw-queues must be in 1..32 (the GPU box refuses GPU_MAX_HW_QUEUES above 32)")
     return a
@@ -905,7 +928,8 @@ class ConfigRun:
         self.streams = [torch.cuda.current_stream()] + [torch.cuda.Stream(device=dev) for _ in range(nst - 1)]
         self.scratch = self._result_set()
         self.res = []
-        self.zseed = os.urandom(32)
+        # the batch equation's randomizer seed: fixed, so that the inputs are the same from run to run
+        self.zseed = hashlib.sha512(b"narwhal_amd bench.py zseed").digest()[:32]
         # C4: the rank's worker-batch digests run inside the timed step on a second stream,
         # concurrently with the verify kernels; the step ends when both are done
         self.ndig = ndig = plan["digest_batches"]
@@ -1109,6 +1133,34 @@ class ConfigRun:
                                    % (self.ndig, nb))
         out["ok"] = not bad and strict and dig_ok
         return out
+
+    def dump_outputs(self, out_dir, budget=64 * 10 ** 6):
+        """What the last timed step computed, as ``out_dir/<name>.npy``: the arrays nw_verify_certs_dev
+        hands its caller (``cert_ok``: verdict per certificate, ``stake``: accepted stake per
+        certificate, ``status``: the input-check word, ``sig_flags``: the NW_F_* bits per vote, all
+        below 2^24 and so exact in float32) and, C4, the step's worker-batch ``digests``.  Called right
+        after run(), before any later leg reuses the buffers.  Ranks above 0 write ``<name>.rank<r>.npy``.
+        ``sig_flags`` is cut to a fixed, seeded sample of the votes when the files would exceed
+        ``budget`` bytes."""
+        import numpy as np
+        i = self.n_step - 1
+        ok, stake, status = self.res[i]
+        arrays = {"cert_ok": ok.cpu().numpy().astype(np.float32),
+                  "stake": stake.cpu().numpy().astype(np.float64),
+                  "status": status.cpu().numpy().astype(np.float32)}
+        if self.ndig:
+            arrays["digests"] = self.d_bouts[i % len(self.d_bouts)].cpu().numpy().astype(np.float32)
+        flags = self.flags[i % self.nst].cpu().numpy()
+        assert int(flags.max(initial=0)) < 1 << 24 and int(flags.min(initial=0)) >= 0
+        room = (budget - sum(a.nbytes for a in arrays.values()) - 4096 * (len(arrays) + 1)) // 4
+        if flags.shape[0] > room:
+            flags = flags[np.sort(np.random.default_rng(0).choice(flags.shape[0], room, replace=False))]
+        arrays["sig_flags"] = flags.astype(np.float32)
+        os.makedirs(out_dir, exist_ok=True)
+        suffix = ".rank%d" % self.rank if self.rank else ""
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+        return {name: list(a.shape) for name, a in arrays.items()}
 
     def isolated(self, launches=3):
         """k_verify launched alone after the timed region, the GPU idle between launches."""
@@ -1315,14 +1367,16 @@ def main(argv=None):
         assert checks.get("ok_all_ranks", checks["ok"]), "honest workload rejected (or a digest mismatched): %r" % checks
     total_sigs = plan["total_sigs"] * args.steps       # every rank's signatures (node-wide)
     value = total_sigs / elapsed
+    dumped = run.dump_outputs(args.dump_outputs) if args.dump_outputs else None
 
     out = None
+    full = args.full               # every leg below that takes runs of its own
     c2 = args.config == "C2"
     cpu_inp = {}
     if rank == 0:
-        iso = run.isolated()
+        iso = run.isolated() if full else None
         roofline = run.roofline(iso, c2)
-        p50c, p99c = cert_latency(run, args.latency_samples)
+        p50c, p99c = cert_latency(run, args.latency_samples) if full else (None, None)
         out = {
             "metric": METRIC, "value": value, "unit": "sigs/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
@@ -1334,10 +1388,13 @@ def main(argv=None):
                        "key_negtab": run.eng.key_negtab(),
                        "parallelism": "certificate shards per GPU; RCCL all_gather of verdict bitmaps + stake"},
             "p50_cert_latency_ms": p50c, "p99_cert_latency_ms": p99c,
-            "roofline": roofline, "checks": checks, "build": _lib.version(),
+            "roofline": roofline, "checks": checks, "build": _lib.version(), "full": full,
         }
+        if dumped is not None:
+            out["outputs_dumped"] = dumped
         if run.ndig:
             out["digest_in_step"] = run.digest_in_step()
+    if rank == 0 and full:
         # GPU legs first: the CPU baselines run more threads than the container's CPU quota, and the
         # cgroup throttling that follows would slow the host side of the next leg
         if world == 1 and c2 and not args.no_extras:
@@ -1353,7 +1410,7 @@ def main(argv=None):
     # share of a 10,000-validator node round (1,250 certificates x 6,667 votes + 1,250 host-resident
     # worker batches), at every world size
     c4run = None
-    if c2 and args.c4_steps > 0:
+    if full and c2 and args.c4_steps > 0:
         run.close()
         c4run = ConfigRun(leg_args(args, "C4"), world, rank, local)
         el4, ch4 = c4run.run(args.c4_steps, args.c4_warmup)
@@ -1362,7 +1419,7 @@ def main(argv=None):
         if rank == 0:
             out["c4"] = c4_block(c4run, el4, ch4, c4run.isolated())
     if rank == 0:
-        if not args.no_cpu_baseline:
+        if full and not args.no_cpu_baseline:
             # every line carries the host baseline, N > 1 included: rank 0 times it after the timed
             # region while the other ranks block in a gloo barrier (a socket wait, no spinning host
             # thread to steal the cores being measured)

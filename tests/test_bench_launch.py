@@ -82,6 +82,18 @@ def test_config_plan_single_rank():
     assert isinstance(args, argparse.Namespace)
 
 
+def test_plain_run_is_the_default_and_steps_are_timed_steps():
+    """``--full`` and ``--dump-outputs`` are off unless given; a run times at least one step."""
+    import pytest
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "0"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 0)
+    a = bench.parse_args(["--full", "--dump-outputs", "somewhere"])
+    assert a.full is True and a.dump_outputs == "somewhere"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
 def test_fm_work_model_matches_kernel_chain():
     """k_verify executes 7 FM per comb position except the chain's first entry (1 FM) and its last
     addition (6 FM, no T): C2 (W24 basepoint, W20 keys) = 7 x (11 + 13 - 1) + 1 - 1 = 161."""

@@ -7,7 +7,7 @@ RE=${2:-k_verify|k_finish|k_sha512}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-CMD=${PMC_CMD:-"python3 bench.py --steps 2 --warmup 1 --c4-steps 0 --no-cpu-baseline --latency-samples 0 ${BENCH_ARGS:-}"}
+CMD=${PMC_CMD:-"python3 bench.py --full --steps 2 --warmup 1 --c4-steps 0 --no-cpu-baseline --latency-samples 0 ${BENCH_ARGS:-}"}
 NPASS=${PMC_PASSES:-5}   # first N counter groups only
 FIRST=${PMC_FIRST:-1}    # skip the groups before this one
 i=0

@@ -7,10 +7,10 @@
 # Output goes to gpurun_out/TAG/.  Steps:
 #   tests[=PYTEST_K]   pytest -m gpu (optionally -k PYTEST_K)          -> gpu_tests.log
 #   smoke              __graft_entry__.smoke()                         -> smoke.log
-#   bench[=ARGS]       bench.py --steps 20 --warmup 5 ARGS             -> bench_<n>.json (n = step index)
-#   c4[=ARGS]          bench.py --config C4 ARGS                       -> bench_c4_<n>.json
+#   bench[=ARGS]       bench.py --full --steps 20 --warmup 5 ARGS      -> bench_<n>.json (n = step index)
+#   c4[=ARGS]          bench.py --full --config C4 ARGS                -> bench_c4_<n>.json
 #   prof_kv            rocprofv3 --kernel-trace --stats over the C2 headline + tools/roofline_rocprof.py
-#   prof[=ARGS]        rocprofv3 --kernel-trace --stats over bench.py ARGS -> prof_<n>/
+#   prof[=ARGS]        rocprofv3 --kernel-trace --stats over bench.py --full ARGS -> prof_<n>/
 #   pmc[=REGEX]        tools/gpu_pmc.sh passes (PMC only with --kernel-trace)
 #   configs=LIST       tools/bench_configs.py --only LIST              -> configs_<n>.jsonl
 #   latency[=ARGS]     tools/latency_probe.py ARGS                     -> latency_<n>.jsonl
@@ -56,12 +56,12 @@ for step in "$@"; do
       cat "$OUT/smoke.log" ;;
     bench)
       # shellcheck disable=SC2086
-      timeout -k 10 "$(lim 600)" python3 -u bench.py --steps 20 --warmup 5 $arg > "$OUT/bench_$n.json" \
+      timeout -k 10 "$(lim 600)" python3 -u bench.py --full --steps 20 --warmup 5 $arg > "$OUT/bench_$n.json" \
         2> "$OUT/bench_$n.err" || die bench "$OUT/bench_$n.err"
       summ "$OUT/bench_$n.json" ;;
     c4)
       # shellcheck disable=SC2086
-      timeout -k 10 "$(lim 900)" python3 -u bench.py --config C4 --steps 10 --warmup 2 $arg > "$OUT/bench_c4_$n.json" \
+      timeout -k 10 "$(lim 900)" python3 -u bench.py --full --config C4 --steps 10 --warmup 2 $arg > "$OUT/bench_c4_$n.json" \
         2> "$OUT/bench_c4_$n.err" || die c4 "$OUT/bench_c4_$n.err"
       summ "$OUT/bench_c4_$n.json" ;;
     prof_kv)
@@ -74,7 +74,7 @@ for step in "$@"; do
     prof)
       # shellcheck disable=SC2086
       timeout -k 10 "$(lim 600)" rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$n" -o p -- \
-        python3 bench.py --no-cpu-baseline --latency-samples 0 $arg > "$OUT/prof_$n.json" 2> "$OUT/prof_$n.log" \
+        python3 bench.py --full --no-cpu-baseline --latency-samples 0 $arg > "$OUT/prof_$n.json" 2> "$OUT/prof_$n.log" \
         || die prof "$OUT/prof_$n.log"
       cut -d, -f1-4 "$OUT/prof_$n/p_kernel_stats.csv" | cut -c1-150 | head -20 ;;
     pmc)
