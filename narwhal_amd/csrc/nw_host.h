@@ -1,0 +1,326 @@
+// Internal types of the C-ABI host layer of libnwcrypto (include/nwcrypto.h), shared by its units:
+//   nw_workspace.cpp  diagnostics, the workspace pool (Lease) and the host-buffer call scope (HostCall)
+//   nw_keycache.cpp   key cache, HBM budget, basepoint-table registry, context create/destroy
+//   nw_staging.cpp    pinned staging (Stager, chunked uploads, message and signature uploads)
+//   nw_api.cpp        the three pipelines and the entry points
+// The pure host arithmetic (layouts, plans) is nw_host_plan.h.
+//
+// Concurrency model (the worker calls from 64 rayon threads,
+// worker/src/processor.rs:75-79):
+//   * the key cache (committee tables, basepoint comb) is shared state behind a reader/writer lock:
+//     every verify call holds it shared while it enqueues; nw_committee_load holds it exclusive and
+//     first waits for every in-flight call that may still read the tables;
+//   * every call leases a Workspace from a pool: its own stream, scratch buffers, pinned staging
+//     buffer and a completion event.  Host-buffer calls run on the workspace's stream and
+//     synchronize it; ``_dev`` calls run on the caller's stream and leave the workspace "pending"
+//     until its event completes — the next lease of that workspace waits on the event (stream
+//     order, or a host wait before any buffer is reallocated), so scratch is never reused while a
+//     kernel may still read it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+#include <condition_variable>
+#include <cstring>
+#include <functional>
+#include <memory>
+#include <mutex>
+#include <optional>
+#include <random>
+#include <shared_mutex>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "nw_host_plan.h"
+#include "nw_kernels.h"
+
+namespace nw {
+
+// A growable buffer that frees itself.  Mem supplies the allocator and the smallest allocation.
+template <class Mem>
+struct Buf {
+    void* p = nullptr;
+    size_t cap = 0;
+    Buf() = default;
+    Buf(Buf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+    Buf& operator=(Buf&& o) noexcept {
+        if (this != &o) {
+            release();
+            std::swap(p, o.p);
+            std::swap(cap, o.cap);
+        }
+        return *this;
+    }
+    ~Buf() { release(); }
+    hipError_t ensure(size_t bytes) {
+        if (bytes <= cap) return hipSuccess;
+        if (p) {
+            hipError_t e = Mem::free(p);
+            if (e != hipSuccess) return e;
+            p = nullptr;
+            cap = 0;
+        }
+        size_t want = bytes < Mem::kMin ? Mem::kMin : bytes + bytes / 4;
+        hipError_t e = Mem::alloc(&p, want);
+        if (e == hipSuccess) cap = want;
+        return e;
+    }
+    void release() {
+        if (p) (void)Mem::free(p);
+        p = nullptr;
+        cap = 0;
+    }
+    template <typename T>
+    T* as() const {
+        return reinterpret_cast<T*>(p);
+    }
+    uint8_t* bytes() const { return as<uint8_t>(); }
+};
+struct DeviceMem {
+    static constexpr size_t kMin = 4096;
+    static hipError_t alloc(void** p, size_t n) { return hipMalloc(p, n); }
+    static hipError_t free(void* p) { return hipFree(p); }
+};
+// Pinned host staging: one DMA per direction for the host-buffer entry points (pageable
+// hipMemcpyAsync stages every call through a driver bounce buffer synchronously).
+struct PinnedMem {
+    static constexpr size_t kMin = 65536;
+    static hipError_t alloc(void** p, size_t n) { return hipHostMalloc(p, n, hipHostMallocDefault); }
+    static hipError_t free(void* p) { return hipHostFree(p); }
+};
+using DevBuf = Buf<DeviceMem>;
+using HostBuf = Buf<PinnedMem>;
+
+// Key-cache map key: the 32 raw key bytes by value (no per-lookup allocation on the one-message
+// paths), hashed with a per-process random seed so chosen keys cannot pile into one bucket.
+struct Key32 {
+    uint64_t w[4];
+    explicit Key32(const uint8_t* p) { std::memcpy(w, p, 32); }
+    bool operator==(const Key32& o) const {
+        return w[0] == o.w[0] && w[1] == o.w[1] && w[2] == o.w[2] && w[3] == o.w[3];
+    }
+};
+struct Key32Hash {
+    static uint64_t seed() {
+        static const uint64_t s = ((uint64_t)std::random_device{}() << 32) ^ std::random_device{}();
+        return s;
+    }
+    static uint64_t mix(uint64_t x) {   // splitmix64 finalizer
+        x ^= x >> 30;
+        x *= 0xBF58476D1CE4E5B9ull;
+        x ^= x >> 27;
+        x *= 0x94D049BB133111EBull;
+        return x ^ (x >> 31);
+    }
+    size_t operator()(const Key32& k) const {
+        uint64_t h = seed();
+        for (uint64_t v : k.w) h = mix(h ^ v);
+        return (size_t)h;
+    }
+};
+
+// Per-call scratch: one per concurrently executing call.  Destroyed (nw_ctx_destroy) with its
+// stream idle and the device set.
+struct Workspace {
+    hipStream_t stream = nullptr;   // stream of host-buffer calls
+    hipEvent_t done = nullptr;      // recorded after the last enqueue that used these buffers
+    hipStream_t last = nullptr;     // stream that event was recorded on
+    bool pending = false;
+    DevBuf w_sig, w_signer, w_keys, w_sig_cert, w_cert_first, w_cert_n, w_msg, w_msg_off, w_msg_len, w_flags,
+        w_slow_count, w_slow_list, w_slow_slot, w_slow_buf, w_cert_ok, w_ok, w_misc, w_out, w_pbuf, w_pre, w_counts,
+        w_cursor, w_perm, w_io, w_var, w_status, w_msm_ent, w_msm_dig, w_msm_zs, w_msm_meta, w_msm_bkt, w_msm_part,
+        w_msm_wpart, w_pslow, w_cert_state, w_exact, w_pinfo;
+    HostBuf h_io, h_meta;
+
+    ~Workspace() {
+        if (done) (void)hipEventDestroy(done);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+    // Grow a buffer; a buffer that may still be read by a pending call is only freed after it.
+    hipError_t ensure(DevBuf& b, size_t bytes) {
+        if (bytes > b.cap && pending) {
+            hipError_t e = hipEventSynchronize(done);
+            if (e != hipSuccess) return e;
+            pending = false;
+        }
+        return b.ensure(bytes);
+    }
+};
+
+constexpr size_t kMaxWorkspaces = 64;   // one per concurrently calling thread (the worker's 64)
+// Asynchronous digest jobs hold a workspace from submit to nw_job_wait; past this many unwaited jobs
+// a submit fails at once (NW_ERR_NOMEM) instead of blocking on a pool that only those jobs' own
+// waits could refill.  The other half of the pool stays for synchronous calls.
+constexpr int kMaxAsyncJobs = (int)kMaxWorkspaces / 2;
+
+}  // namespace nw
+
+struct nw_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;   // administrative stream: basepoint table, committee loads
+    uint32_t finish_k = 0;          // k_finish signatures per lane (0: adaptive, finish_k_for)
+    // key cache (shared by all calls; guarded by keys_mu)
+    std::shared_mutex keys_mu;
+    uint32_t* d_btab = nullptr;
+    size_t max_keys = 0;          // 0: derived from the HBM budget once the window is fixed
+    bool max_keys_user = false;
+    int key_window = 0;           // 0: not yet decided (first load)
+    bool committee_mode = false;  // nw_opts.key_window == -1
+    bool key_reserve = false;     // committee mode + max_keys: the first load allocates max_keys slots
+    bool budget_fixed = false;    // window, max_keys and reservation decided (first load with keys)
+    size_t key_words = 0;         // u32 words per key-cache slot (T+, and T- when key_negtab)
+    bool key_negtab = false;      // each key table followed by its negated copy (k_verify: no negation)
+    uint32_t opt_flags = 0;       // nw_opts.flags (NW_OPT_*)
+    size_t nkeys = 0, key_cap = 0;
+    uint32_t* d_keys_raw = nullptr;
+    uint32_t* d_key_info = nullptr;
+    uint32_t* d_stake = nullptr;
+    uint32_t* d_key_tab = nullptr;
+    std::unordered_map<nw::Key32, uint32_t, nw::Key32Hash> slot_of;
+    std::vector<uint32_t> h_stake;
+    nw::DevBuf w_bases;           // committee-load scratch (exclusive lock)
+    // workspace pool
+    std::mutex pool_mu;
+    std::condition_variable pool_cv;
+    std::vector<std::unique_ptr<nw::Workspace>> pool;
+    std::vector<nw::Workspace*> free_ws;
+    std::atomic<int> async_jobs{0};   // unwaited nw_sha512_many_async jobs (<= kMaxAsyncJobs)
+    // measurement: (start, stop) event pairs around k_verify launches
+    std::mutex prof_mu;
+    bool prof_on = false;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
+    size_t prof_used = 0;
+    uint64_t prof_sigs = 0;
+};
+
+namespace nw {
+
+// Diagnostics are per calling thread (a context is shared by many threads).
+void set_error(nw_ctx* ctx, const std::string& msg);
+const char* last_error();
+int fail(nw_ctx* ctx, hipError_t e, const char* what);
+
+#define NW_TRY(expr, what)                                \
+    do {                                                  \
+        hipError_t e_ = (expr);                           \
+        if (e_ != hipSuccess) return fail(ctx, e_, what); \
+    } while (0)
+// a step that reports for itself (NW_* code, error text set)
+#define NW_RC(expr)                     \
+    do {                                \
+        int rc_ = (expr);               \
+        if (rc_ != NW_OK) return rc_;   \
+    } while (0)
+
+// Lease of a workspace for one call.  ``bind(st)`` orders the call after the workspace's previous
+// user; ``finish(st)`` records the completion event (kept pending for asynchronous calls).  A
+// host-buffer call that fails after enqueueing synchronizes its stream on release, so no DMA from
+// its pinned buffer and no kernel on its scratch outlives the call.
+//
+// Which free workspace a call gets: one whose last work was on the call's own stream (stream order
+// already serializes them), else one with no work in flight, else a new one while the pool is below
+// kMaxWorkspaces.  So device-buffer calls alternating over two streams (one batch's k_finish and
+// slow path under the next batch's k_verify) run on two workspaces and never wait for each other;
+// only a full pool falls back to the most recently freed workspace and its completion event.
+class Lease {
+public:
+    // pinned_hint: bytes of pinned staging the call will need; an idle workspace that already has
+    // them is preferred (growing a pinned buffer costs ~0.1 s per GB of pinning, and the first DMAs
+    // from new pinned pages stall: a 1,250-batch worker window on a workspace grown mid-run ran at
+    // half the rate, r04w).
+    explicit Lease(nw_ctx* ctx, hipStream_t st = nullptr, size_t pinned_hint = 0);
+    ~Lease();
+    Lease(const Lease&) = delete;
+    Lease& operator=(const Lease&) = delete;
+    // Bind the leased workspace to st, or to its own stream; NW_ERR_DEVICE (error text set) when
+    // no workspace could be had.
+    int open(hipStream_t st, bool sync_on_release);
+    int open(bool sync_on_release) { return open(ws_ ? ws_->stream : nullptr, sync_on_release); }
+    Workspace* ws() const { return ws_; }
+    hipStream_t stream() const { return stream_; }
+    hipError_t finish();
+    // a host-buffer call that completed: its stream is idle
+    void synced();
+
+private:
+    nw_ctx* ctx_;
+    Workspace* ws_ = nullptr;
+    hipStream_t stream_ = nullptr;
+    bool sync_on_release_ = false;
+};
+
+// Scope of one host-buffer call: the device set, the key lock held shared, a workspace leased and
+// bound to its own stream.  ``open`` takes the device and the lock (checks that read the key cache
+// go between it and ``lease``); ``begin`` is both; ``finish`` waits for the call's work.  Leaving
+// the scope without finish() (an error return) drains the stream before the workspace is reused.
+class HostCall {
+public:
+    explicit HostCall(nw_ctx* ctx) : ctx_(ctx) {}
+    int open();
+    int lease();
+    int begin() {
+        NW_RC(open());
+        return lease();
+    }
+    int finish();
+    Workspace* ws = nullptr;
+    hipStream_t st = nullptr;
+
+private:
+    nw_ctx* ctx_;
+    std::shared_lock<std::shared_mutex> keys_;   // released after the lease
+    std::optional<Lease> lease_;
+};
+
+// Wait for every call that may still read the key tables (exclusive key lock held).
+int drain_all(nw_ctx* ctx);
+
+// Key cache (nw_keycache.cpp).  Slots of keys already in the cache (shared lock held): true when
+// every key is cached.
+bool lookup_slots(nw_ctx* ctx, const uint8_t (*pk)[32], size_t n, uint32_t* slots);
+
+// Host-buffer inputs of one call: segments are packed into the workspace's pinned buffer (256-B
+// aligned) and copied to their device buffers with asynchronous DMAs, so a call issues no
+// pageable copies and no intermediate synchronization (the call's final stream sync releases the
+// buffer).  Every segment is staged, large ones included: the runtime's pageable H2D runs at the
+// pinned rate only for host pages it has already seen; the first copy from a fresh buffer pins its
+// pages and took 7-10 ms per 8 MB on MI355X (profiles/r04/host_fed_trace_r04h.txt), and a node's
+// input buffers are fresh on every call (network receives).  The staging memcpy costs ~0.3 ms per
+// 8 MB at 31-34 GB/s (tools/host_fed_probe.py).
+// A call reserves the bytes it will stage before its first segment; a segment past that capacity
+// fails the call (NW_ERR_DEVICE, "staging overflow") instead of writing past the pinned buffer.
+class Stager {
+public:
+    Stager(nw_ctx* ctx, Workspace* ws, hipStream_t st) : ctx_(ctx), ws_(ws), st_(st) {}
+    int reserve(size_t bytes);
+    static size_t room(size_t bytes) { return align256(bytes); }
+    uint8_t* alloc(size_t n);   // null (error text set) past the reservation
+    int copy(void* dst, const uint8_t* h, size_t n, const char* what);
+    int put(void* dst, const void* src, size_t n, const char* what);
+
+private:
+    nw_ctx* ctx_;
+    Workspace* ws_;
+    hipStream_t st_;
+    size_t off_ = 0, cap_ = 0;
+};
+
+// Chunk c covers staging bytes [cb[c], cb[c+1]); copy_chunk(c) fills it; the DMAs go out in chunk
+// order, each as soon as its chunk is staged (large uploads are staged by several threads).
+hipError_t stage_chunks(size_t nch, const size_t* cb, const std::function<void(size_t)>& copy_chunk, const uint8_t* h,
+                        uint8_t* d, hipStream_t st);
+// Upload n bytes of host memory through pinned staging at h in kStageChunk chunks.
+hipError_t staged_h2d(uint8_t* h, uint8_t* dst, const uint8_t* src, size_t n, hipStream_t st);
+size_t message_bytes(const size_t* len, size_t n);
+// Pack per-signature messages into the workspace (MSGMODE 1).  fixed_len (MSM callers, whose kernel
+// reads either form): messages of one length laid out back to back go up as one block with no
+// offset / length arrays (*fixed_len = the length; UINT64_MAX otherwise).
+int upload_messages(nw_ctx* ctx, Workspace* ws, Stager& sg, const uint8_t* const* msg, const size_t* len, size_t n,
+                    size_t total, uint64_t* fixed_len = nullptr);
+// Upload per-signature messages, signatures and raw keys to the workspace (uncached-key paths).
+int upload_sig_keys(nw_ctx* ctx, Workspace* ws, const uint8_t* const* msg, const size_t* len,
+                    const uint8_t (*pk)[32], const uint8_t (*sig)[64], size_t n, hipStream_t st,
+                    uint64_t* fixed_len = nullptr);
+
+}  // namespace nw

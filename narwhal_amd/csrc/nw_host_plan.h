@@ -1,0 +1,241 @@
+// Host-side planning of the C-ABI layer: everything a call decides with plain arithmetic before it
+// touches the GPU.  Range validation, the staging-buffer layouts (each defined once: the same
+// definition gives the byte count that sizes a buffer and the offsets that fill it), the preamble
+// state of a small call, the MSM task plan, the asynchronous digest's chunk boundaries, the key comb
+// window and the k_finish lane depth.  No runtime call: compiles for the host alone (hipcc
+// --cuda-host-only, or g++ with the ROCm include path) and is tested on the CPU
+// (tests/test_host_plan.py).
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+#include <utility>
+#include <vector>
+
+#include "nw_kernels.h"
+#include "nw_msm.h"
+
+namespace nw {
+
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// Segments of a staging block at 256-byte aligned offsets, in the order they are taken; ``end`` is
+// the size of the block so far.
+struct Bump {
+    size_t end = 0;
+    size_t take(size_t bytes) {
+        const size_t o = end;
+        end = align256(o + bytes);
+        return o;
+    }
+};
+
+// Calls below this many signatures (and whose staged bytes fit kSmallCallBytes) upload their
+// preamble state (PreLayout): the signer grouping (k_expand_count's histogram) only runs from
+// kGroupMinSigs up.
+constexpr size_t kStagedMaxSigs = 16384;
+// Calls whose whole input fits this many bytes take the one-DMA small-call path.
+constexpr size_t kSmallCallBytes = 2u << 20;
+// Pinned staging goes up in chunks of this size, each chunk's DMA issued as soon as it is staged.
+constexpr size_t kStageChunk = 4u << 20;
+
+// Certificate / batch vote ranges must be pairwise disjoint: a vote belongs to at most one
+// certificate (its coefficient z and its exact-path term are keyed by that certificate).  Empty
+// ranges never overlap anything.
+inline bool ranges_disjoint(const uint32_t* first, const uint32_t* nv, size_t n) {
+    std::vector<std::pair<uint64_t, uint64_t>> r;
+    r.reserve(n);
+    for (size_t c = 0; c < n; ++c)
+        if (nv[c]) r.emplace_back(first[c], (uint64_t)first[c] + nv[c]);
+    std::sort(r.begin(), r.end());
+    for (size_t k = 1; k < r.size(); ++k)
+        if (r[k].first < r[k - 1].second) return false;
+    return true;
+}
+
+// Preamble state a small host-buffer call uploads with its inputs (one DMA), so the batch starts
+// with no preamble kernels: the vote -> certificate map (host-expanded), the zeroed slow-path
+// counter and the zeroed per-certificate exact-path state.
+struct PreLayout {
+    Bump b;
+    size_t sig_cert, zero4, cert_state;   // [nsigs + 1] u32 | [4] u32 | [ncerts] u32
+    PreLayout(size_t nsigs, size_t ncerts)
+        : sig_cert(b.take((nsigs + 1) * 4)), zero4(b.take(16)), cert_state(b.take(ncerts * 4 + 4)) {}
+    size_t bytes() const { return b.end; }
+};
+struct PreStaged {
+    uint32_t* sig_cert;
+    uint32_t* zero4;
+    uint32_t* cert_state;
+    PreStaged(uint8_t* d, const PreLayout& l)
+        : sig_cert(reinterpret_cast<uint32_t*>(d + l.sig_cert)), zero4(reinterpret_cast<uint32_t*>(d + l.zero4)),
+          cert_state(reinterpret_cast<uint32_t*>(d + l.cert_state)) {}
+};
+// Fill the block at h.  The ranges are host-validated: inside [0, nsigs), disjoint.
+inline void prestage(uint8_t* h, const PreLayout& l, const uint32_t* first, const uint32_t* nv, size_t ncerts,
+                     size_t nsigs) {
+    std::memset(h, 0, l.bytes());
+    uint32_t* sc = reinterpret_cast<uint32_t*>(h + l.sig_cert);
+    std::memset(sc, 0xFF, (nsigs + 1) * 4);   // NO_CERT: votes outside every range
+    for (size_t c = 0; c < ncerts; ++c) {
+        const size_t f = first[c], e = f + nv[c];
+        for (size_t v = f; v < e; ++v) sc[v] = (uint32_t)c;
+    }
+}
+
+// One-DMA layout of a small cached-key call (run_generic): n signatures with per-signature
+// messages of ``total`` bytes, all in one "certificate"; both outputs come back in one D2H.
+struct PackedLayout {
+    PreLayout pl;
+    Bump in, out;
+    size_t msg, off, len, sig, signer, fn, pre;   // fn: the (first, n_votes) word pair
+    size_t cert_ok, ok;
+    PackedLayout(size_t total, size_t n)
+        : pl(n, 1), msg(in.take(total + 8)), off(in.take(n * 8)), len(in.take(n * 8)), sig(in.take(n * 64)),
+          signer(in.take(n * 4)), fn(in.take(8)), pre(in.take(pl.bytes())), cert_ok(out.take(1)), ok(out.take(n)) {}
+};
+inline bool small_call(size_t n, size_t total) {
+    return n <= kStagedMaxSigs && PackedLayout(total, n).in.end < kSmallCallBytes;
+}
+
+// Input and output blocks of nw_verify_certs; ``staged`` calls carry the preamble state.
+struct CertsLayout {
+    bool staged;
+    PreLayout pl;
+    Bump in, out;
+    size_t sig, signer, first, nv, msg, pre;
+    size_t cert_ok, stake, ok;
+    CertsLayout(size_t nsigs, size_t ncerts)
+        : staged(nsigs <= kStagedMaxSigs), pl(nsigs, ncerts), sig(in.take(nsigs * 64)), signer(in.take(nsigs * 4)),
+          first(in.take(ncerts * 4)), nv(in.take(ncerts * 4)), msg(in.take(ncerts * 32)),
+          pre(in.take(staged ? pl.bytes() : 0)), cert_ok(out.take(ncerts)), stake(out.take(ncerts * 8)),
+          ok(out.take(nsigs)) {}
+};
+
+// Staged block of per-signature messages (upload_messages): the packed bytes, offsets, lengths.
+struct MessageLayout {
+    Bump b;
+    size_t packed, off, len;
+    MessageLayout(size_t total, size_t n) : packed(b.take(total + 8)), off(b.take(n * 8 + 8)), len(b.take(n * 8 + 8)) {}
+    size_t bytes() const { return b.end; }
+};
+
+// Pinned block of a digest call: offsets, lengths and the message bytes go up; the n digests come
+// back either behind the data (asynchronous jobs: the block lives until nw_job_wait) or over the
+// start of the block once the uploads are done (out_behind false).
+struct DigestLayout {
+    Bump b;
+    size_t off, len, data, out, out_end;
+    DigestLayout(size_t n, size_t data_bytes, bool out_behind)
+        : off(b.take(n * 8)), len(b.take(n * 8)), data(b.take(data_bytes)), out(out_behind ? b.take(n * 64) : 0),
+          out_end(align256(out + n * 64)) {}
+    size_t bytes() const { return std::max(b.end, out_end); }
+};
+
+// Asynchronous digest: the messages packed at 16-byte aligned offsets, cut into chunks of whole
+// messages, each closed once it holds >= kStageChunk bytes.  Chunk c covers packed bytes
+// [cb[c], cb[c + 1]) and messages [cm[c], cm[c + 1]); no chunk when nothing is packed.
+struct DigestPack {
+    std::vector<uint64_t> off;
+    size_t total = 0;
+    std::vector<size_t> cb{0}, cm{0};
+    size_t chunks() const { return cb.size() - 1; }
+};
+inline DigestPack digest_pack(const size_t* len, size_t n) {
+    DigestPack p;
+    p.off.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        p.off[i] = p.total;
+        p.total += (len[i] + 15) & ~(size_t)15;
+    }
+    for (size_t i = 0; i < n; ++i) {
+        const size_t packed = i + 1 < n ? (size_t)p.off[i + 1] : p.total;
+        if (packed - p.cb.back() >= kStageChunk || (i + 1 == n && packed > p.cb.back())) {
+            p.cb.push_back(packed);
+            p.cm.push_back(i + 1);
+        }
+    }
+    return p;
+}
+
+// Task plan of the segmented Pippenger MSM (nw_msm.hip) over nb consecutive batches (batch b = the
+// next counts[b] signatures).  Entries of batch b with first signature f: R entries [2f, 2f + c),
+// A entries [2f + c, 2f + 2c).  Windows below msm_nwin_r(C) cover both (z_i < 2^128 multiplies R),
+// the rest only the A entries; every (batch, window) is cut into tasks of at most MSM_CH entries.
+struct MsmPlan {
+    uint32_t C = 0, NA = 0, NR = 0;   // window bits (8 from 512 signatures in the largest batch), windows
+    std::vector<uint32_t> bfirst, bcount, sig_batch, wfirst;
+    std::vector<MsmTask> tasks;
+    uint32_t one_task_windows = 1;    // see MsmParams
+};
+inline MsmPlan msm_plan(const uint32_t* counts, size_t nb, size_t nsig) {
+    MsmPlan p;
+    uint32_t nmax = 0;
+    for (size_t b = 0; b < nb; ++b) nmax = std::max(nmax, counts[b]);
+    p.C = nmax >= 512 ? 8 : 7;
+    p.NA = (uint32_t)msm_nwin_a((int)p.C);
+    p.NR = (uint32_t)msm_nwin_r((int)p.C);
+    p.bfirst.resize(nb);
+    p.bcount.resize(nb);
+    p.sig_batch.resize(nsig);
+    p.wfirst.resize(nb * p.NA + 1);
+    size_t f = 0;
+    for (size_t b = 0; b < nb; ++b) {
+        p.bfirst[b] = (uint32_t)f;
+        p.bcount[b] = counts[b];
+        for (uint32_t t = 0; t < counts[b]; ++t) p.sig_batch[f + t] = (uint32_t)b;
+        for (uint32_t j = 0; j < p.NA; ++j) {
+            p.wfirst[b * p.NA + j] = (uint32_t)p.tasks.size();
+            const size_t lo = 2 * f + (j < p.NR ? 0 : counts[b]), hi = 2 * f + 2 * (size_t)counts[b];
+            for (size_t e = lo; e < hi; e += MSM_CH) {
+                const size_t e1 = std::min(e + MSM_CH, hi);
+                p.tasks.push_back(MsmTask{(uint32_t)e, (uint32_t)e1, j, (uint32_t)p.tasks.size()});
+            }
+        }
+        f += counts[b];
+    }
+    p.wfirst[nb * p.NA] = (uint32_t)p.tasks.size();
+    for (size_t k = 0; k < nb * p.NA; ++k)
+        if (p.wfirst[k + 1] - p.wfirst[k] != 1u || p.wfirst[k] != k) p.one_task_windows = 0;
+    return p;
+}
+// Metadata block of an MSM call: bfirst | bcount | sig_batch | wfirst | tasks | bad flags.
+struct MsmMetaLayout {
+    Bump b;
+    size_t bfirst, bcount, sig_batch, wfirst, tasks, bad;
+    MsmMetaLayout(size_t nb, size_t nsig, const MsmPlan& p)
+        : bfirst(b.take(nb * 4)), bcount(b.take(nb * 4)), sig_batch(b.take(nsig * 4 + 4)),
+          wfirst(b.take(p.wfirst.size() * 4)), tasks(b.take(p.tasks.size() * sizeof(MsmTask) + 16)),
+          bad(b.take(nb * 4)) {}
+    size_t bytes() const { return b.end; }
+};
+
+// Key comb window, fixed at the first load.  Committee mode (nw_opts.key_window -1): the widest
+// window (fewest additions per signature) whose tables fit the budget for ``n`` keys times
+// ``headroom``; ``table_words(w)`` is the u32 words of one key's table (comb_words); 8 when none fits.
+template <class TableWords>
+int committee_window(size_t n, double headroom, size_t budget, TableWords table_words) {
+    for (int w : {20, 16, 13, 12, 9}) {
+        const double need = headroom * (double)n * (double)table_words(w) * 4.0;
+        if (need <= (double)budget) return w;
+    }
+    return 8;
+}
+
+// Signatures per k_finish lane for a launch of n (``fixed``: a pinned value, 0 = adaptive): just
+// enough that the lanes fit one wave per SIMD, because below that the kernel is bound by the serial
+// prefix-product chain + inversion of each lane, not by the inversion count.  k_finish<ONE> up to
+// one lane per SIMD slot (256 CUs x 4 SIMDs x 64); above, the chunked kernel (four waves per SIMD)
+// with the fewest signatures per lane (2 .. FINISH_K) that still fits the chip in one round.  A
+// single certificate (67 .. 6,667 signatures) gets one signature per lane: one inversion per
+// signature, no chain; C2's million signatures get 16 per lane.
+inline uint32_t finish_k_for(uint32_t fixed, size_t n) {
+    if (fixed) return fixed;
+    const size_t one_max = 256 * 4 * 64, lanes = one_max * 4;
+    if (n <= one_max) return 1;
+    const size_t k = (n + lanes - 1) / lanes;
+    return k < 2 ? 2u : (k > (size_t)FINISH_K ? (uint32_t)FINISH_K : (uint32_t)k);
+}
+
+}  // namespace nw

@@ -1,0 +1,110 @@
+// Stand-alone driver of narwhal_amd/csrc/nw_host_plan.h for a sanitizer build (tests/test_host_plan.py
+// compiles it with -fsanitize=address,undefined and runs it): every buffer is allocated at exactly
+// the size the layout reports, so a fill that runs past its layout is a heap overflow report.
+// Exit status 0 = every shape ran and its basic invariants held.
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+#include "nw_host_plan.h"
+
+using namespace nw;
+
+static int failures = 0;
+#define CHECK(cond)                                                   \
+    do {                                                              \
+        if (!(cond)) {                                                \
+            std::fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #cond); \
+            ++failures;                                               \
+        }                                                             \
+    } while (0)
+
+static void check_prestage(const std::vector<uint32_t>& first, const std::vector<uint32_t>& nv, size_t nsigs) {
+    const size_t ncerts = first.size();
+    CHECK(ranges_disjoint(first.data(), nv.data(), ncerts));
+    const PreLayout l(nsigs, ncerts);
+    std::vector<uint8_t> h(l.bytes(), 0xAB);
+    prestage(h.data(), l, first.data(), nv.data(), ncerts, nsigs);
+    const uint32_t* sc = reinterpret_cast<const uint32_t*>(h.data() + l.sig_cert);
+    size_t claimed = 0, want = 0;
+    for (size_t v = 0; v < nsigs; ++v) claimed += sc[v] != NO_CERT;
+    for (size_t c = 0; c < ncerts; ++c) want += nv[c];
+    CHECK(claimed == want);
+    CHECK(sc[nsigs] == NO_CERT);
+    for (size_t i = 0; i < 16; ++i) CHECK(h[l.zero4 + i] == 0);
+    for (size_t i = 0; i < ncerts * 4 + 4; ++i) CHECK(h[l.cert_state + i] == 0);
+    // the same block inside the two call layouts that carry it
+    const CertsLayout cl(nsigs, ncerts);
+    std::vector<uint8_t> in(cl.in.end);
+    if (cl.staged) prestage(in.data() + cl.pre, cl.pl, first.data(), nv.data(), ncerts, nsigs);
+    CHECK(cl.ok + nsigs <= cl.out.end && cl.stake + ncerts * 8 <= cl.ok);
+}
+
+static void check_msm(const std::vector<uint32_t>& counts) {
+    size_t nsig = 0;
+    for (uint32_t c : counts) nsig += c;
+    const MsmPlan p = msm_plan(counts.data(), counts.size(), nsig);
+    const MsmMetaLayout ml(counts.size(), nsig, p);
+    std::vector<uint8_t> meta(ml.bytes());
+    std::memcpy(meta.data() + ml.bfirst, p.bfirst.data(), counts.size() * 4);
+    std::memcpy(meta.data() + ml.bcount, p.bcount.data(), counts.size() * 4);
+    if (nsig) std::memcpy(meta.data() + ml.sig_batch, p.sig_batch.data(), nsig * 4);
+    std::memcpy(meta.data() + ml.wfirst, p.wfirst.data(), p.wfirst.size() * 4);
+    if (!p.tasks.empty()) std::memcpy(meta.data() + ml.tasks, p.tasks.data(), p.tasks.size() * sizeof(MsmTask));
+    CHECK(ml.bad + counts.size() * 4 <= ml.bytes());
+    CHECK(p.wfirst.back() == p.tasks.size());
+    for (const MsmTask& t : p.tasks) CHECK(t.e0 < t.e1 && t.e1 - t.e0 <= (uint32_t)MSM_CH && t.e1 <= 2 * nsig);
+}
+
+static void check_digest(const std::vector<size_t>& len) {
+    const DigestPack p = digest_pack(len.data(), len.size());
+    const DigestLayout l(len.size(), p.total, true);
+    CHECK(l.out + len.size() * 64 <= l.bytes());
+    CHECK(p.cb.size() == p.cm.size());
+    CHECK(p.cb.back() == (p.chunks() ? p.total : 0));
+    // pack one byte per message end: stays inside the data segment
+    std::vector<uint8_t> h(l.bytes());
+    for (size_t c = 0; c < p.chunks(); ++c)
+        for (size_t i = p.cm[c]; i < p.cm[c + 1]; ++i)
+            if (len[i]) h[l.data + p.off[i] + len[i] - 1] = 1;
+}
+
+int main() {
+    const uint32_t top = 0xFFFFFFFFu;
+    {
+        const uint32_t f[] = {top - 10, 0, 5, 5}, n[] = {10, 5, 0, 3};
+        CHECK(ranges_disjoint(f, n, 4));
+        const uint32_t f2[] = {0, 4}, n2[] = {5, 2};
+        CHECK(!ranges_disjoint(f2, n2, 2));
+    }
+    check_prestage({0}, {1}, 1);
+    check_prestage({0, 7, 9}, {4, 0, 3}, 14);
+    {
+        std::vector<uint32_t> f(128), n(128, 128);
+        for (uint32_t c = 0; c < 128; ++c) f[c] = c * 128;
+        check_prestage(f, n, 16384);
+        f.push_back(16384);
+        n.push_back(1);
+        check_prestage(f, n, 16385);
+    }
+    for (const auto& counts : std::vector<std::vector<uint32_t>>{{1}, {0, 5, 0}, {511}, {512}, {1024}, {1025}, {67, 1025, 3}})
+        check_msm(counts);
+    const size_t M4 = (size_t)4 << 20;
+    check_digest({});
+    check_digest({0, 0});
+    check_digest({M4 - 16, 16, 1, 0, M4 + 1});
+    check_digest(std::vector<size_t>(1250, 508052));
+    for (size_t total : {(size_t)0, (size_t)5, (size_t)(2u << 20) - 8192 + 5, (size_t)(2u << 20) + 5}) {
+        const PackedLayout l(total, 3);
+        const MessageLayout m(total, 3);
+        CHECK(l.pre + l.pl.bytes() == l.in.end && m.len + 3 * 8 + 8 <= m.bytes());
+        CHECK(small_call(3, total) == (l.in.end < kSmallCallBytes));
+    }
+    auto words = [](int w) { return (size_t)((256 + w - 1) / w) * ((1u << (w - 1)) + 1) * 32; };
+    CHECK(committee_window(10000, 1.25, (size_t)200 << 30, words) == 13);
+    CHECK(committee_window(1, 1.0, 0, words) == 8);
+    CHECK(finish_k_for(0, 65536) == 1 && finish_k_for(0, 65537) == 2 && finish_k_for(0, 262144 * 16 + 1) == FINISH_K);
+    if (failures) return 1;
+    std::puts("host plan ok");
+    return 0;
+}

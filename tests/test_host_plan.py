@@ -1,0 +1,447 @@
+"""CPU: the host planning of the C-ABI layer (narwhal_amd/csrc/nw_host_plan.h): range validation, the
+preamble state of small calls, the staging layouts, the MSM task plan, the asynchronous digest's
+chunking, the committee window and the k_finish lane depth.  The header is compiled for the host
+into a small shim (as tests/test_host_scalar.py does) and every expected value is restated here in
+Python.  The same header also runs under AddressSanitizer + UBSan as a stand-alone program
+(tests/host_plan_check.cpp); nothing sanitized is loaded into Python.
+"""
+import ctypes
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "narwhal_amd", "csrc")
+HIPCC = "/opt/rocm/bin/hipcc"
+NO_CERT = 0xFFFFFFFF
+MSM_CH = 2048
+MIB = 1 << 20
+
+SRC = r"""
+#include "nw_host_plan.h"
+#include "nw_point.h"
+using namespace nw;
+extern "C" {
+int t_ranges_disjoint(const uint32_t* f, const uint32_t* n, size_t k) { return ranges_disjoint(f, n, k) ? 1 : 0; }
+// offsets then the size, per layout
+void t_pre_layout(size_t nsigs, size_t ncerts, size_t* o) {
+    const PreLayout l(nsigs, ncerts);
+    o[0] = l.sig_cert; o[1] = l.zero4; o[2] = l.cert_state; o[3] = l.bytes();
+}
+void t_prestage(const uint32_t* f, const uint32_t* n, size_t ncerts, size_t nsigs, uint8_t* h) {
+    prestage(h, PreLayout(nsigs, ncerts), f, n, ncerts, nsigs);
+}
+void t_packed_layout(size_t total, size_t n, size_t* in, size_t* out) {
+    const PackedLayout l(total, n);
+    in[0] = l.msg; in[1] = l.off; in[2] = l.len; in[3] = l.sig; in[4] = l.signer; in[5] = l.fn; in[6] = l.pre;
+    in[7] = l.in.end;
+    out[0] = l.cert_ok; out[1] = l.ok; out[2] = l.out.end;
+}
+int t_small_call(size_t n, size_t total) { return small_call(n, total) ? 1 : 0; }
+int t_certs_layout(size_t nsigs, size_t ncerts, size_t* in, size_t* out) {
+    const CertsLayout l(nsigs, ncerts);
+    in[0] = l.sig; in[1] = l.signer; in[2] = l.first; in[3] = l.nv; in[4] = l.msg; in[5] = l.pre; in[6] = l.in.end;
+    out[0] = l.cert_ok; out[1] = l.stake; out[2] = l.ok; out[3] = l.out.end;
+    return l.staged ? 1 : 0;
+}
+void t_message_layout(size_t total, size_t n, size_t* o) {
+    const MessageLayout l(total, n);
+    o[0] = l.packed; o[1] = l.off; o[2] = l.len; o[3] = l.bytes();
+}
+void t_digest_layout(size_t n, size_t data, int behind, size_t* o) {
+    const DigestLayout l(n, data, behind != 0);
+    o[0] = l.off; o[1] = l.len; o[2] = l.data; o[3] = l.out; o[4] = l.bytes();
+}
+// head: C, NA, NR, one_task_windows, ntasks; meta: the metadata block's offsets then its size
+int t_msm_plan(const uint32_t* counts, size_t nb, size_t nsig, uint32_t* head, uint32_t* bfirst, uint32_t* bcount,
+               uint32_t* sig_batch, uint32_t* wfirst, uint32_t* tasks, size_t task_cap, size_t* meta) {
+    const MsmPlan p = msm_plan(counts, nb, nsig);
+    if (p.tasks.size() > task_cap) return -1;
+    head[0] = p.C; head[1] = p.NA; head[2] = p.NR; head[3] = p.one_task_windows; head[4] = (uint32_t)p.tasks.size();
+    std::memcpy(bfirst, p.bfirst.data(), nb * 4);
+    std::memcpy(bcount, p.bcount.data(), nb * 4);
+    std::memcpy(sig_batch, p.sig_batch.data(), nsig * 4);
+    std::memcpy(wfirst, p.wfirst.data(), p.wfirst.size() * 4);
+    std::memcpy(tasks, p.tasks.data(), p.tasks.size() * sizeof(MsmTask));
+    const MsmMetaLayout l(nb, nsig, p);
+    meta[0] = l.bfirst; meta[1] = l.bcount; meta[2] = l.sig_batch; meta[3] = l.wfirst; meta[4] = l.tasks;
+    meta[5] = l.bad; meta[6] = l.bytes();
+    return 0;
+}
+long t_digest_pack(const size_t* len, size_t n, uint64_t* off, size_t* total, size_t* cb, size_t* cm, size_t cap) {
+    const DigestPack p = digest_pack(len, n);
+    if (p.cb.size() > cap) return -1;
+    std::memcpy(off, p.off.data(), n * 8);
+    *total = p.total;
+    std::memcpy(cb, p.cb.data(), p.cb.size() * sizeof(size_t));
+    std::memcpy(cm, p.cm.data(), p.cm.size() * sizeof(size_t));
+    return (long)p.chunks();
+}
+int t_committee_window(size_t n, double headroom, size_t budget) {
+    return committee_window(n, headroom, budget, comb_words);
+}
+uint32_t t_finish_k_for(uint32_t fixed, size_t n) { return finish_k_for(fixed, n); }
+int t_finish_k_max() { return FINISH_K; }
+}
+"""
+
+
+@pytest.fixture(scope="module")
+def lib(tmp_path_factory):
+    if not os.path.exists(HIPCC) or shutil.which("ld") is None:
+        pytest.skip("hipcc not available")
+    d = tmp_path_factory.mktemp("plan")
+    src = d / "plan.hip"
+    src.write_text(SRC)
+    so = d / "libplan.so"
+    subprocess.run([HIPCC, "-O2", "-std=c++17", "-fPIC", "-shared", "--cuda-host-only", "-I", CSRC, str(src),
+                    "-o", str(so)], check=True, capture_output=True)
+    L = ctypes.CDLL(str(so))
+    L.t_committee_window.argtypes = [ctypes.c_size_t, ctypes.c_double, ctypes.c_size_t]
+    L.t_finish_k_for.argtypes = [ctypes.c_uint32, ctypes.c_size_t]
+    L.t_finish_k_for.restype = ctypes.c_uint32
+    L.t_small_call.argtypes = [ctypes.c_size_t, ctypes.c_size_t]
+    L.t_digest_pack.restype = ctypes.c_long
+    return L
+
+
+def _u32(a):
+    return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+def _p(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _sz(n):
+    return ctypes.c_size_t(n)
+
+
+def _sizes(k):
+    return (ctypes.c_size_t * k)()
+
+
+def align256(x):
+    return (x + 255) & ~255
+
+
+def check_block(offsets, sizes, total):
+    """Segments at 256-byte aligned offsets, none overlapping, the block ending where the last ends."""
+    segs = sorted(zip(offsets, sizes))
+    end = 0
+    for o, s in segs:
+        assert o % 256 == 0
+        assert o >= end or s == 0, (segs, o)
+        end = max(end, o + s)
+    assert total == align256(end), (segs, total)
+
+
+# ---------------------------------------------------------------- ranges_disjoint
+
+def _disjoint_n2(first, nv):
+    r = [(f, f + n) for f, n in zip(first, nv) if n]
+    return not any(a[0] < b[1] and b[0] < a[1] for i, a in enumerate(r) for b in r[i + 1:])
+
+
+TOP = 2**32 - 1
+RANGE_CASES = [
+    ([], []),
+    ([0], [0]),
+    ([0, 5, 5], [5, 0, 3]),              # an empty range next to others, touching ranges
+    ([0, 3], [10, 0]),                   # an empty range inside another
+    ([0, 9], [10, 4]),                   # a one-vote overlap
+    ([9, 0], [4, 10]),                   # the same, unsorted
+    ([0, 10], [10, 10]),                 # touching
+    ([TOP - 10, 0], [10, 5]),            # first + n = 2^32 - 1
+    ([TOP - 10, TOP - 1], [10, 1]),      # one-vote overlap at the top
+    ([TOP - 10, TOP], [10, 0]),
+    ([7, 7], [1, 1]),
+    ([7, 7], [0, 0]),
+]
+
+
+def test_ranges_disjoint_cases(lib):
+    for first, nv in RANGE_CASES:
+        got = lib.t_ranges_disjoint(_p(_u32(first)), _p(_u32(nv)), _sz(len(first)))
+        assert bool(got) == _disjoint_n2(first, nv), (first, nv)
+
+
+def test_ranges_disjoint_random(lib):
+    rng = np.random.default_rng(3)
+    seen = set()
+    for _ in range(400):
+        k = int(rng.integers(1, 7))
+        first = [int(x) for x in rng.integers(0, 24, k)]
+        nv = [int(x) for x in rng.integers(0, 6, k)]
+        want = _disjoint_n2(first, nv)
+        seen.add(want)
+        assert bool(lib.t_ranges_disjoint(_p(_u32(first)), _p(_u32(nv)), _sz(k))) == want, (first, nv)
+    assert seen == {True, False}
+
+
+# ---------------------------------------------------------------- prestage
+
+def _shape_128x128(extra):
+    first = [c * 128 for c in range(128)] + ([16384] if extra else [])
+    nv = [128] * 128 + ([1] if extra else [])
+    return first, nv, 16384 + extra
+
+
+PRESTAGE_SHAPES = [([0], [1], 1),
+                   ([0, 7, 9], [4, 0, 3], 14),      # a gap [4, 7), an empty certificate, votes past the last range
+                   _shape_128x128(0)]
+
+
+@pytest.mark.parametrize("first,nv,nsigs", PRESTAGE_SHAPES, ids=["1x1", "gap-empty", "16384"])
+def test_prestage_matches_python(lib, first, nv, nsigs):
+    ncerts = len(first)
+    o = _sizes(4)
+    lib.t_pre_layout(_sz(nsigs), _sz(ncerts), o)
+    o_sc, o_z, o_cs, total = list(o)
+    check_block([o_sc, o_z, o_cs], [(nsigs + 1) * 4, 16, ncerts * 4 + 4], total)
+    h = np.full(total, 0xAB, dtype=np.uint8)
+    lib.t_prestage(_p(_u32(first)), _p(_u32(nv)), _sz(ncerts), _sz(nsigs), _p(h))
+    want = [NO_CERT] * (nsigs + 1)
+    for c in range(ncerts):
+        for v in range(first[c], first[c] + nv[c]):
+            want[v] = c
+    got = h[o_sc:o_sc + (nsigs + 1) * 4].view(np.uint32)
+    assert got.tolist() == want
+    assert not h[o_z:o_z + 16].any()
+    assert not h[o_cs:o_cs + ncerts * 4 + 4].any()
+    assert not h[o_sc + (nsigs + 1) * 4:].any()      # padding, zero block and state block alike
+
+
+# ---------------------------------------------------------------- layouts
+
+def _packed(lib, total, n):
+    i, o = _sizes(8), _sizes(3)
+    lib.t_packed_layout(_sz(total), _sz(n), i, o)
+    return list(i), list(o)
+
+
+def _pre_bytes(nsigs, ncerts):
+    return align256((nsigs + 1) * 4) + 256 + align256(ncerts * 4 + 4)
+
+
+def _packed_in_bytes(total, n):
+    return (align256(total + 8) + 2 * align256(n * 8) + align256(n * 64) + align256(n * 4) + 256
+            + _pre_bytes(n, 1))
+
+
+@pytest.mark.parametrize("total,n", [(0, 1), (5, 3), (1000, 7), (2 * MIB - 8192 + 5, 3), (2 * MIB + 5, 3),
+                                     (32 * 16384, 16384)])
+def test_packed_layout(lib, total, n):
+    i, o = _packed(lib, total, n)
+    check_block(i[:7], [total + 8, n * 8, n * 8, n * 64, n * 4, 8, _pre_bytes(n, 1)], i[7])
+    assert i[7] == _packed_in_bytes(total, n)
+    check_block(o[:2], [1, n], o[2])
+
+
+def test_small_call_flips_where_the_one_dma_layout_reaches_2mib(lib):
+    n = 3
+    flip = next(t for t in range(2 * MIB - 16384, 2 * MIB, 1) if _packed_in_bytes(t, n) >= 2 * MIB)
+    assert _packed_in_bytes(flip - 1, n) < 2 * MIB <= _packed_in_bytes(flip, n)
+    for t in (0, 5, flip - 257, flip - 1, flip, flip + 1, flip + 256, 4 * MIB):
+        assert bool(lib.t_small_call(n, t)) == (_packed_in_bytes(t, n) < 2 * MIB), t
+        assert _packed(lib, t, n)[0][7] == _packed_in_bytes(t, n)
+    assert lib.t_small_call(n, flip - 1) == 1 and lib.t_small_call(n, flip) == 0
+    # the message lengths tests/test_gpu_host_paths.py uses sit on either side
+    assert lib.t_small_call(3, 5 + 2 * MIB - 8192) == 1 and lib.t_small_call(3, 5 + 2 * MIB) == 0
+    # and the signature limit
+    assert lib.t_small_call(16384, 0) == 1 and lib.t_small_call(16385, 0) == 0
+
+
+@pytest.mark.parametrize("nsigs,ncerts", [(1, 1), (14, 3), (16384, 128), (16385, 129), (0, 1), (100000, 1500)])
+def test_certs_layout(lib, nsigs, ncerts):
+    i, o = _sizes(7), _sizes(4)
+    staged = lib.t_certs_layout(_sz(nsigs), _sz(ncerts), i, o)
+    assert bool(staged) == (nsigs <= 16384)
+    pre = _pre_bytes(nsigs, ncerts) if staged else 0
+    check_block(list(i)[:6], [nsigs * 64, nsigs * 4, ncerts * 4, ncerts * 4, ncerts * 32, pre], i[6])
+    check_block(list(o)[:3], [ncerts, ncerts * 8, nsigs], o[3])
+
+
+@pytest.mark.parametrize("total,n", [(0, 0), (8, 1), (5, 3), (2 * MIB + 5, 3), (500000, 62500)])
+def test_message_layout(lib, total, n):
+    o = _sizes(4)
+    lib.t_message_layout(_sz(total), _sz(n), o)
+    check_block(list(o)[:3], [total + 8, n * 8 + 8, n * 8 + 8], o[3])
+
+
+@pytest.mark.parametrize("n,data", [(1, 0), (1, 13), (5, 2 * MIB + 1), (1250, 1250 * 508064)])
+def test_digest_layouts(lib, n, data):
+    o = _sizes(5)
+    lib.t_digest_layout(_sz(n), _sz(data), 1, o)        # asynchronous: the digests behind the data
+    check_block(list(o)[:4], [n * 8, n * 8, data, n * 64], o[4])
+    lib.t_digest_layout(_sz(n), _sz(data), 0, o)        # synchronous: the digests over the start of the block
+    check_block(list(o)[:3], [n * 8, n * 8, data], align256(o[2] + data))
+    assert o[3] == 0 and o[4] == max(align256(o[2] + data), align256(n * 64))
+
+
+# ---------------------------------------------------------------- MSM plan
+
+def _msm(lib, counts):
+    nb, nsig = len(counts), sum(counts)
+    head = np.zeros(5, np.uint32)
+    bfirst, bcount = np.zeros(nb, np.uint32), np.zeros(nb, np.uint32)
+    sig_batch = np.zeros(max(nsig, 1), np.uint32)
+    wfirst = np.zeros(nb * 40 + 1, np.uint32)
+    cap = 1 << 16
+    tasks = np.zeros((cap, 4), np.uint32)
+    meta = _sizes(7)
+    rc = lib.t_msm_plan(_p(_u32(counts)), _sz(nb), _sz(nsig), _p(head), _p(bfirst), _p(bcount), _p(sig_batch),
+                        _p(wfirst), _p(tasks), _sz(cap), meta)
+    assert rc == 0
+    C, NA, NR, one, ntasks = (int(x) for x in head)
+    return dict(C=C, NA=NA, NR=NR, one=one, tasks=tasks[:ntasks].tolist(), bfirst=bfirst.tolist(),
+                bcount=bcount.tolist(), sig_batch=sig_batch[:nsig].tolist(), wfirst=wfirst[:nb * NA + 1].tolist(),
+                meta=list(meta))
+
+
+@pytest.mark.parametrize("counts", [[1], [0, 5, 0], [511], [512], [1024], [1025], [67, 1025, 3]], ids=str)
+def test_msm_plan_invariants(lib, counts):
+    p = _msm(lib, counts)
+    nb, nsig = len(counts), sum(counts)
+    C = 8 if max(counts) >= 512 else 7
+    NA, NR = -(-254 // C), -(-129 // C)
+    assert (p["C"], p["NA"], p["NR"]) == (C, NA, NR)
+    assert p["bcount"] == counts
+    assert p["bfirst"] == [sum(counts[:b]) for b in range(nb)]
+    assert p["sig_batch"] == [b for b in range(nb) for _ in range(counts[b])]
+    wf, tasks = p["wfirst"], p["tasks"]
+    assert wf[0] == 0 and wf[-1] == len(tasks) and all(a <= b for a, b in zip(wf, wf[1:]))
+    assert [t[3] for t in tasks] == list(range(len(tasks)))          # each task's partial is its own index
+    one = True
+    for b in range(nb):
+        f, c = p["bfirst"][b], counts[b]
+        for win in range(NA):
+            k = b * NA + win
+            mine = tasks[wf[k]:wf[k + 1]]
+            lo, hi = (2 * f if win < NR else 2 * f + c), 2 * f + 2 * c
+            pos = lo
+            for e0, e1, w, _ in mine:                               # an exact tiling in pieces of <= MSM_CH
+                assert w == win and e0 == pos and e0 < e1 <= hi and e1 - e0 <= MSM_CH
+                pos = e1
+            assert pos == hi or (not mine and lo == hi)
+            assert len(mine) == -(-(hi - lo) // MSM_CH)
+            one = one and len(mine) == 1 and wf[k] == k
+    assert p["one"] == int(one)
+    m = p["meta"]
+    check_block(m[:6], [nb * 4, nb * 4, nsig * 4 + 4, (nb * NA + 1) * 4, len(tasks) * 16 + 16, nb * 4], m[6])
+
+
+def test_msm_one_task_windows_boundary(lib):
+    assert _msm(lib, [1024])["one"] == 1                             # 2,048 entries: one task per window
+    p = _msm(lib, [1025])
+    assert p["one"] == 0 and len(p["tasks"]) == 2 * p["NR"] + (p["NA"] - p["NR"])
+    assert _msm(lib, [0, 5, 0])["one"] == 0                          # empty batches have no task
+
+
+# ---------------------------------------------------------------- asynchronous digest chunks
+
+def _pack(lib, lens):
+    n = len(lens)
+    ln = np.ascontiguousarray(lens, dtype=np.uint64)
+    off = np.zeros(max(n, 1), np.uint64)
+    cap = 4096
+    cb, cm = _sizes(cap), _sizes(cap)
+    total = ctypes.c_size_t(0)
+    nch = lib.t_digest_pack(_p(ln), _sz(n), _p(off), ctypes.byref(total), cb, cm, _sz(cap))
+    assert nch >= 0
+    return off[:n].tolist(), total.value, list(cb)[:nch + 1], list(cm)[:nch + 1]
+
+
+@pytest.mark.parametrize("lens", [[], [0, 0], [4 * MIB - 16, 16, 1, 0, 4 * MIB + 1], [508052] * 1250],
+                         ids=["none", "empty-messages", "edges", "worker-window"])
+def test_digest_chunks(lib, lens):
+    off, total, cb, cm = _pack(lib, lens)
+    n = len(lens)
+    want_off, pos = [], 0
+    for ln in lens:                                                  # 16-byte aligned packing
+        want_off.append(pos)
+        pos += (ln + 15) // 16 * 16
+    assert off == want_off and total == pos
+    assert cb[0] == 0 and cm[0] == 0
+    if total == 0:
+        assert cb == [0] and cm == [0]                               # no chunk
+        return
+    assert cb[-1] == total and cm[-1] == n                           # cover [0, total), every message
+    ends = want_off[1:] + [total]
+    for c in range(len(cb) - 1):
+        assert cm[c] < cm[c + 1] and cb[c] < cb[c + 1]               # contiguous, whole messages
+        assert cb[c] == (want_off[cm[c]] if cm[c] < n else total)
+        assert cb[c + 1] == ends[cm[c + 1] - 1]
+        if c + 1 < len(cb) - 1:
+            assert cb[c + 1] - cb[c] >= 4 * MIB                      # every chunk but the last
+            if cm[c + 1] - cm[c] > 1:                                # ... closed by the first message that gets there
+                assert ends[cm[c + 1] - 2] - cb[c] < 4 * MIB
+
+
+# ---------------------------------------------------------------- committee window, k_finish depth
+
+def _comb_words(w):
+    return -(-256 // w) * ((1 << (w - 1)) + 1) * 32
+
+
+def _window(n, num, den, budget):
+    """The widest of 20, 16, 13, 12, 9 whose tables fit num/den * n keys in budget bytes, else 8."""
+    for w in (20, 16, 13, 12, 9):
+        if num * n * _comb_words(w) * 4 <= budget * den:
+            return w
+    return 8
+
+
+def test_committee_window_table(lib):
+    for n in (1, 40, 10000, 200000):
+        for headroom, num, den in ((1.0, 1, 1), (1.25, 5, 4)):
+            for w in (20, 16, 13, 12, 9):
+                need = num * n * _comb_words(w) * 4 // den          # exact: words is a multiple of 32
+                for budget in (need, need - 1, need + 1):
+                    assert lib.t_committee_window(n, headroom, budget) == _window(n, num, den, budget), (n, w, budget)
+                assert lib.t_committee_window(n, headroom, need) == w
+            assert lib.t_committee_window(n, headroom, 0) == 8
+    assert lib.t_committee_window(10000, 1.25, 200 << 30) == 13      # a 10,000-key committee on one GPU
+
+
+def test_finish_k_for_table(lib):
+    kmax = lib.t_finish_k_max()
+    assert kmax == 16
+    one_max, lanes = 256 * 4 * 64, 256 * 4 * 64 * 4
+
+    def want(fixed, n):
+        if fixed:
+            return fixed
+        if n <= one_max:
+            return 1
+        return min(max(-(-n // lanes), 2), kmax)
+
+    for n in (0, 1, 65536, 65537, lanes, lanes + 1, 2 * lanes, 2 * lanes + 1, 262144 * 16, 262144 * 16 + 1, 10**8):
+        for fixed in (0, 1, 5, 16):
+            assert lib.t_finish_k_for(fixed, n) == want(fixed, n), (fixed, n)
+    assert [lib.t_finish_k_for(0, n) for n in (65536, 65537, 262144 * 16 + 1)] == [1, 2, 16]
+
+
+# ---------------------------------------------------------------- sanitizer run (stand-alone program)
+
+def test_host_plan_under_sanitizers(tmp_path):
+    """tests/host_plan_check.cpp drives the same header over the shapes above as an ordinary
+    executable built with ASan + UBSan: exit status 0 and no report."""
+    cxx = shutil.which("g++")
+    if cxx:
+        cmd = [cxx, "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include"]
+    elif os.path.exists(HIPCC):
+        cmd = [HIPCC, "--cuda-host-only", "-x", "hip"]
+    else:
+        pytest.skip("no host compiler")
+    exe = tmp_path / "host_plan_check"
+    subprocess.run(cmd + ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-I", CSRC,
+                          os.path.join(ROOT, "tests", "host_plan_check.cpp"), "-o", str(exe)],
+                   check=True, capture_output=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "host plan ok" in r.stdout
+    assert "runtime error" not in r.stderr and "Sanitizer" not in r.stderr, r.stderr[-2000:]

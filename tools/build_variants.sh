@@ -3,6 +3,7 @@
 # Usage: bash tools/build_variants.sh NAME "EXTRA_HIPCC_FLAGS" [NAME "FLAGS" ...]
 # REBUILD="obj1.o obj2.o" limits the recompiled objects (the others are copied from the default
 # build, which must be current): e.g. REBUILD="nw_kv_w20.o nw_kvs_w20.o" for a k_verify A/B at C2.
+# The host-layer defines live in nw_api.o (NW_GROUP_SIGNERS) and nw_keycache.o (NW_FK_FIXED).
 # build_exp/ is in .gpurunignore: remove that line for the call that runs the A/B.
 set -e
 cd "$(dirname "$0")/../narwhal_amd/csrc"
