@@ -331,6 +331,89 @@ int nw_certificates_verify(nw_ctx* ctx, const nw_committee* committee, const uin
                            const size_t* len, size_t n, const uint8_t zseed[32], uint64_t cert_base,
                            int32_t* verdict);
 
+/* ---- Core message path: mixed batches --------------------------------
+ * What the reference's ``Core`` does with each received ``PrimaryMessage`` (primary/src/core.rs:306-346:
+ * sanitize_header, sanitize_vote, sanitize_certificate, one message at a time), for many Header, Vote
+ * and Certificate frames in arrival order: one NW_DAG_* verdict per frame, every check in the
+ * reference's order.  The host half decodes and runs every check that needs no crypto; the GPU half
+ * runs all the crypto as ONE stream-ordered submission (one upload, the digest / link / strict /
+ * certificate / verdict kernels, one download, one synchronization).
+ *   Header       TooOld (gc_round > round, core.rs:307-310); then Header::verify
+ *                (primary/src/messages.rs:48-67): id, UnknownAuthority, MalformedHeader, strict signature.
+ *   Vote         TooOld (current.round > round, core.rs:321-324); UnexpectedVote (:327-333); then
+ *                Vote::verify (messages.rs:131-142): UnknownAuthority, strict signature over the vote digest.
+ *   Certificate  TooOld (core.rs:339-342); then Certificate::verify (messages.rs:189-215): genesis is
+ *                Ok; the Header steps; AuthorityReuse / UnknownAuthority / CertificateRequiresQuorum;
+ *                the batch equation.
+ *   An undecodable frame is NW_DAG_SERIALIZATION (no state check applies to it). */
+#define NW_DAG_TOO_OLD 9                /* DagError::TooOld */
+#define NW_DAG_UNEXPECTED_VOTE 10       /* DagError::UnexpectedVote */
+#define NW_DAG_NOT_CORE_MESSAGE 11      /* a well-formed PrimaryMessage variant other than Header, Vote or
+                                           Certificate (the reference panics there, core.rs:374) */
+
+/* nw_core_view.kind */
+#define NW_CORE_HEADER 0
+#define NW_CORE_VOTE 1
+#define NW_CORE_CERTIFICATE 2
+#define NW_CORE_OTHER 3                 /* undecodable, or not a Core message */
+
+/* The part of Core's mutable state the sanitize_* checks read (core.rs:307,321-333,339): the
+ * garbage-collection round and the header this primary is collecting votes for.  Passing NULL for
+ * the state skips those checks (TooOld, UnexpectedVote): the caller then applies them when it applies
+ * the verdicts, against the state at that moment. */
+typedef struct nw_core_state {
+    uint64_t gc_round;
+    uint8_t id[32];        /* current_header.id */
+    uint64_t round;        /* current_header.round */
+    uint8_t author[32];    /* current_header.author */
+} nw_core_state;
+
+typedef struct nw_core_batch nw_core_batch;
+
+/* Decoded view of one message of a batch.  Pointers stay valid until nw_core_batch_free; those of
+ * fields a kind does not have (and every pointer of an undecodable frame) are NULL. */
+typedef struct nw_core_view {
+    int32_t kind;                    /* NW_CORE_* */
+    int32_t status;                  /* NW_DAG_PENDING, or the verdict decided on the host */
+    int32_t header_error;            /* Header, Certificate: UNKNOWN_AUTHORITY / MALFORMED_HEADER or NW_DAG_OK */
+    int32_t quorum_error;            /* Certificate: AUTHORITY_REUSE / UNKNOWN_AUTHORITY / REQUIRES_QUORUM or OK */
+    uint64_t round;
+    const uint8_t* author;           /* 32 B: header author; Vote: the voter */
+    const uint8_t* id;               /* 32 B: header id; Vote: the id voted for */
+    const uint8_t* origin;           /* 32 B: Vote: the header's author; else = author */
+    const uint8_t* signature;        /* 64 B: header signature; Vote: the vote's */
+    const uint8_t* preimage;         /* digest preimage: Hash for Header (messages.rs:70-84: author ||
+                                        round || payload || parents); Vote: Hash for Vote (:145-153, 72 B) */
+    size_t preimage_len;
+    const uint8_t* cert_preimage;    /* Certificate: 72 B, Hash for Certificate (:226-234) */
+    uint32_t first_vote, n_votes;    /* Certificate */
+    const uint8_t* vote_keys;        /* [n_votes][32] */
+    const uint8_t* vote_sigs;        /* [n_votes][64] */
+} nw_core_view;
+
+/* Host only (no context, no GPU): decode n frames and run every host-side check of core.rs:306-346,
+ * messages.rs:48-67, :131-142 and :189-215 (everything but digests and signatures). */
+int nw_core_batch_decode(const nw_committee* committee, const nw_core_state* state, const uint8_t* const* frame,
+                         const size_t* len, size_t n, nw_core_batch** out);
+size_t nw_core_batch_size(const nw_core_batch* batch);
+int nw_core_batch_view(const nw_core_batch* batch, size_t i, nw_core_view* out);
+void nw_core_batch_free(nw_core_batch* batch);
+/* The GPU half of core.rs:306-346 (the digests and signatures of messages.rs:48-67, :131-142,
+ * :189-215), one submission: verdict[i] receives the NW_DAG_* verdict of message i.  When the host
+ * decided every message nothing is launched and no device is needed (ctx may then be NULL).
+ * Batch coefficients (NW-Z v1): the certificates that enter the batch step are those still pending
+ * after decoding with header_error == quorum_error == NW_DAG_OK; the j-th of them, in arrival order,
+ * uses batch index cert_base + j, and *certs_used (may be NULL) receives their number, so the caller
+ * advances cert_base by it.  A certificate whose header then fails on the device (id or signature)
+ * still uses up its index (unlike nw_cert_batch_verify, which numbers certificates after the header
+ * checks).  zseed == NULL is NW_ERR_ARG. */
+int nw_core_batch_verify(nw_ctx* ctx, const nw_core_batch* batch, const uint8_t zseed[32], uint64_t cert_base,
+                         int32_t* verdict, uint64_t* certs_used);
+/* decode + verify + free in one call: what Core::sanitize_* (core.rs:306-346) returns per frame. */
+int nw_core_messages_verify(nw_ctx* ctx, const nw_committee* committee, const nw_core_state* state,
+                            const uint8_t* const* frame, const size_t* len, size_t n, const uint8_t zseed[32],
+                            uint64_t cert_base, int32_t* verdict, uint64_t* certs_used);
+
 /* Library build identifier (gfx target, build date). */
 const char* nw_version(void);
 /* NW_ABI_VERSION the library was built with. */

@@ -55,12 +55,29 @@ class NwCertView(ctypes.Structure):
 DAG_PENDING, DAG_OK, DAG_INVALID_SIGNATURE, DAG_SERIALIZATION, DAG_INVALID_HEADER_ID = -1, 0, 1, 2, 3
 DAG_MALFORMED_HEADER, DAG_UNKNOWN_AUTHORITY, DAG_AUTHORITY_REUSE, DAG_REQUIRES_QUORUM = 4, 5, 6, 7
 DAG_NOT_CERTIFICATE = 8
+DAG_TOO_OLD, DAG_UNEXPECTED_VOTE, DAG_NOT_CORE_MESSAGE = 9, 10, 11
+CORE_HEADER, CORE_VOTE, CORE_CERTIFICATE, CORE_OTHER = 0, 1, 2, 3   # nw_core_view.kind
+
+
+class NwCoreState(ctypes.Structure):
+    _fields_ = [("gc_round", ctypes.c_uint64), ("id", ctypes.c_uint8 * 32), ("round", ctypes.c_uint64),
+                ("author", ctypes.c_uint8 * 32)]
+
+
+class NwCoreView(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int32), ("status", ctypes.c_int32), ("header_error", ctypes.c_int32),
+                ("quorum_error", ctypes.c_int32), ("round", ctypes.c_uint64), ("author", ctypes.c_void_p),
+                ("id", ctypes.c_void_p), ("origin", ctypes.c_void_p), ("signature", ctypes.c_void_p),
+                ("preimage", ctypes.c_void_p), ("preimage_len", ctypes.c_size_t), ("cert_preimage", ctypes.c_void_p),
+                ("first_vote", ctypes.c_uint32), ("n_votes", ctypes.c_uint32), ("vote_keys", ctypes.c_void_p),
+                ("vote_sigs", ctypes.c_void_p)]
 
 ABI_VERSION = 2    # NW_ABI_VERSION of include/nwcrypto.h this binding is written against
 
 _OPTIONAL = {"nw_abi_version", "nw_profile_read_sigs", "nw_base_window", "nw_cert_batch_decode", "nw_cert_batch_size",
              "nw_cert_batch_view", "nw_cert_batch_free", "nw_cert_batch_verify", "nw_certificates_verify",
-             "nw_sha512_many_async", "nw_job_done", "nw_job_wait"}
+             "nw_sha512_many_async", "nw_job_done", "nw_job_wait", "nw_core_batch_decode", "nw_core_batch_size",
+             "nw_core_batch_view", "nw_core_batch_free", "nw_core_batch_verify", "nw_core_messages_verify"}
 
 
 def _load() -> ctypes.CDLL:
@@ -106,6 +123,14 @@ def _load() -> ctypes.CDLL:
         "nw_cert_batch_free": (None, [P]),
         "nw_cert_batch_verify": (I, [P, P, P, U64, P]),
         "nw_certificates_verify": (I, [P, ctypes.POINTER(NwCommittee), P, P, S, P, U64, P]),
+        "nw_core_batch_decode": (I, [ctypes.POINTER(NwCommittee), ctypes.POINTER(NwCoreState), P, P, S,
+                                     ctypes.POINTER(P)]),
+        "nw_core_batch_size": (S, [P]),
+        "nw_core_batch_view": (I, [P, S, ctypes.POINTER(NwCoreView)]),
+        "nw_core_batch_free": (None, [P]),
+        "nw_core_batch_verify": (I, [P, P, P, U64, P, ctypes.POINTER(U64)]),
+        "nw_core_messages_verify": (I, [P, ctypes.POINTER(NwCommittee), ctypes.POINTER(NwCoreState), P, P, S, P, U64, P,
+                                        ctypes.POINTER(U64)]),
     }
     for name, (res, args) in sig.items():
         if name in _OPTIONAL and not hasattr(lib, name):
@@ -506,6 +531,33 @@ class Engine:
                    "nw_cert_batch_verify")
         return list(out[:n])
 
+    # -- Core message path (nw_core_batch_verify) ------------------------------------------------
+    def core_batch_verify(self, batch: "CoreFrameBatch", zseed: bytes, cert_base: int = 0):
+        """(NW_DAG_* verdict per message of a decoded mixed batch, certificates that used a batch
+        index): every digest and signature in one GPU submission."""
+        n = len(batch)
+        out = (ctypes.c_int32 * max(n, 1))()
+        used = ctypes.c_uint64(0)
+        self.check(LIB.nw_core_batch_verify(self._ctx, batch.handle, _buf(bytes(zseed)), cert_base, out,
+                                            ctypes.byref(used)), "nw_core_batch_verify")
+        return list(out[:n]), used.value
+
+    def core_messages_verify(self, committee: "CommitteeABI", state: Optional[NwCoreState], frames, zseed: bytes,
+                             cert_base: int = 0):
+        """nw_core_messages_verify: decode + verify + free in one ABI call; returns (verdicts,
+        certificates that used a batch index)."""
+        frames = [bytes(f) for f in frames]
+        n = len(frames)
+        ptrs = (ctypes.c_char_p * max(n, 1))(*frames)
+        lens = (ctypes.c_size_t * max(n, 1))(*[len(f) for f in frames])
+        out = (ctypes.c_int32 * max(n, 1))()
+        used = ctypes.c_uint64(0)
+        self.check(LIB.nw_core_messages_verify(self._ctx, ctypes.byref(committee.struct),
+                                               ctypes.byref(state) if state is not None else None, ptrs, lens, n,
+                                               _buf(bytes(zseed)), cert_base, out, ctypes.byref(used)),
+                   "nw_core_messages_verify")
+        return list(out[:n]), used.value
+
 
 class DigestJob:
     """One nw_sha512_many_async submission in flight.  ``done()`` polls; ``wait()`` returns the
@@ -615,6 +667,64 @@ class CertBatch:
     def close(self):
         if self._h:
             LIB.nw_cert_batch_free(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def core_state(gc_round: int, header_id: bytes, header_round: int, header_author: bytes) -> NwCoreState:
+    """nw_core_state: Core's gc_round and the header it is collecting votes for."""
+    return NwCoreState(gc_round, (ctypes.c_uint8 * 32)(*bytes(header_id)), header_round,
+                       (ctypes.c_uint8 * 32)(*bytes(header_author)))
+
+
+class CoreFrameBatch:
+    """Host-side decode of a mixed batch of Header / Vote / Certificate frames and every host check
+    of Core::sanitize_* (nw_core_batch_decode: C++, no GPU).  ``state`` None skips the checks against
+    Core's mutable state (TooOld, UnexpectedVote)."""
+
+    def __init__(self, committee: CommitteeABI, frames, state: Optional[NwCoreState] = None):
+        frames = [bytes(f) for f in frames]
+        n = len(frames)
+        self._frames = frames
+        ptrs = (ctypes.c_char_p * max(n, 1))(*frames)
+        lens = (ctypes.c_size_t * max(n, 1))(*[len(f) for f in frames])
+        self._h = ctypes.c_void_p()
+        rc = LIB.nw_core_batch_decode(ctypes.byref(committee.struct), ctypes.byref(state) if state is not None else None,
+                                      ptrs, lens, n, ctypes.byref(self._h))
+        if rc != NW_OK:
+            raise DeviceError("nw_core_batch_decode failed (rc=%d)" % rc)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def __len__(self):
+        return LIB.nw_core_batch_size(self._h)
+
+    def view(self, i: int) -> dict:
+        v = NwCoreView()
+        if LIB.nw_core_batch_view(self._h, i, ctypes.byref(v)) != NW_OK:
+            raise IndexError(i)
+
+        def rd(p, k):
+            return ctypes.string_at(p, k) if p and k else (b"" if p else None)
+        votes = None
+        if v.kind == CORE_CERTIFICATE:
+            votes = [(ctypes.string_at(v.vote_keys + 32 * j, 32), ctypes.string_at(v.vote_sigs + 64 * j, 64))
+                     for j in range(v.n_votes)]
+        return {"kind": v.kind, "status": v.status, "header_error": v.header_error, "quorum_error": v.quorum_error,
+                "round": v.round, "author": rd(v.author, 32), "id": rd(v.id, 32), "origin": rd(v.origin, 32),
+                "signature": rd(v.signature, 64), "preimage": rd(v.preimage, v.preimage_len),
+                "cert_preimage": rd(v.cert_preimage, 72), "votes": votes}
+
+    def close(self):
+        if self._h:
+            LIB.nw_core_batch_free(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):

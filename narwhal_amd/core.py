@@ -12,6 +12,10 @@ error are what the serial loop would have produced:
 * ``primary.verify_certificates`` for the certificates (its own SHA-512, strict and
   certificate-batch submissions).
 
+``sanitize_frames`` and ``CoreBatcher.submit_frames`` are the native forms of the same two steps: they
+take the wire frames, decode and host-check them in C++ and run every digest and signature in ONE GPU
+submission (``nw_core_messages_verify``).
+
 Only the verdict/stake consumers of ``process_vote`` / ``process_certificate`` are mirrored
 (``VotesAggregator`` / ``CertificatesAggregator``, primary/src/aggregators.rs); storage, network,
 synchronizer and consensus hand-off are out of scope.  Host logic only: every digest
@@ -24,8 +28,8 @@ from typing import Callable, Dict, Iterable, List, Optional, Sequence, Tuple
 
 from . import _lib
 from .primary import (AuthorityReuse, Certificate, Committee, DagError, Header, InvalidHeaderId,
-                      InvalidSignature, MalformedHeader, UnknownAuthority, Vote, committee_slots,
-                      verify_certificates)
+                      InvalidSignature, MalformedHeader, SerializationError, UnknownAuthority, Vote, _DAG_KIND,
+                      committee_abi, committee_slots, decode_primary_message, verify_certificates)
 
 
 class TooOld(DagError):
@@ -169,6 +173,44 @@ def sanitize_messages(messages: Sequence, committee: Committee, gc_round: int, c
     return [s if s is not None else e for s, e in zip(stale, errs)]
 
 
+class NotACoreMessage(DagError):
+    """A well-formed PrimaryMessage that is not a Header, Vote or Certificate (the reference's Core
+    panics on it, primary/src/core.rs:374; the native frame path reports it)."""
+
+
+_CORE_KIND = dict(_DAG_KIND)
+_CORE_KIND.update({_lib.DAG_TOO_OLD: TooOld, _lib.DAG_UNEXPECTED_VOTE: UnexpectedVote,
+                   _lib.DAG_NOT_CORE_MESSAGE: NotACoreMessage})
+
+
+def _errors(codes: Sequence[int]) -> List[Optional[DagError]]:
+    return [None if c == _lib.DAG_OK else _CORE_KIND[c]() for c in codes]
+
+
+def decode_core_frames(frames: Sequence[bytes], committee: Committee, gc_round: Optional[int] = None,
+                       current_header: Optional[Header] = None) -> "_lib.CoreFrameBatch":
+    """Native (C++) decode + every host check of Core::sanitize_* for a mixed batch of frames (no
+    GPU).  With ``gc_round`` None the checks against Core's state are skipped."""
+    state = None
+    if gc_round is not None:
+        state = _lib.core_state(gc_round, current_header.id, current_header.round, current_header.author)
+    return _lib.CoreFrameBatch(committee_abi(committee), frames, state)
+
+
+def sanitize_frames(frames: Sequence[bytes], committee: Committee, gc_round: int, current_header: Header,
+                    engine=None, zseed: Optional[bytes] = None, cert_base: int = 0) -> List[Optional[DagError]]:
+    """``sanitize_messages`` on the wire frames, natively: C++ decode and host checks, then every
+    digest and signature in ONE GPU submission (nw_core_messages_verify).  Returns None (Ok) or the
+    DagError per frame, in the reference's check order.  Batch coefficients: the j-th certificate
+    that passes its host checks uses batch index ``cert_base + j`` (include/nwcrypto.h)."""
+    eng = engine or _lib.default_engine()
+    if zseed is None:
+        zseed = os.urandom(32)
+    state = _lib.core_state(gc_round, current_header.id, current_header.round, current_header.author)
+    codes, _ = eng.core_messages_verify(committee_abi(committee), state, frames, zseed, cert_base)
+    return _errors(codes)
+
+
 class CoreBatcher:
     """The verdict-consuming part of ``Core`` (primary/src/core.rs:24-73) driven in batches.
 
@@ -236,6 +278,30 @@ class CoreBatcher:
 
     def submit(self, messages: Sequence, zseed: Optional[bytes] = None):
         return self._apply(messages, self._check(messages, zseed))
+
+    def submit_frames(self, frames: Sequence[bytes], zseed: Optional[bytes] = None):
+        """``submit`` on the wire frames: the state-independent checks run natively (C++ decode, one
+        GPU submission, no state: nw_core_messages_verify with a NULL state), then ``_apply`` runs
+        the state checks and the aggregators on the decoded messages in arrival order.  A frame
+        that is not a decodable Core message keeps its native verdict (SerializationError /
+        NotACoreMessage).  Returns what ``submit`` returns on the decoded objects."""
+        if zseed is None:
+            zseed = os.urandom(32)
+        codes, used = self.engine.core_messages_verify(committee_abi(self.committee), None, frames, zseed,
+                                                       self.cert_base)
+        self.cert_base += used
+        checked = _errors(codes)
+        errs: List[Optional[DagError]] = list(checked)
+        at, msgs = [], []
+        for i, (f, e) in enumerate(zip(frames, checked)):
+            if isinstance(e, (SerializationError, NotACoreMessage)):
+                continue
+            at.append(i)
+            msgs.append(decode_primary_message(f))
+        applied, assembled, parents = self._apply(msgs, [checked[i] for i in at])
+        for i, e in zip(at, applied):
+            errs[i] = e
+        return errs, assembled, parents
 
     def pipeline(self, batches: Iterable[Sequence], zseed: Optional[bytes] = None,
                  before_apply: Optional[Callable[[int, "CoreBatcher"], None]] = None):

@@ -1,6 +1,7 @@
 // C-ABI entry points of libnwcrypto (include/nwcrypto.h) and the three launch pipelines behind them:
 // the certificate pipeline on cached keys, the strict variable-base verify and the MSM for keys
-// outside the cache.  No CPU compute path: every verdict and digest comes from the GPU.  The types,
+// outside the cache.  (The fourth pipeline, the mixed Core batch built on the first, is
+// nw_corepipe.cpp.)  No CPU compute path: every verdict and digest comes from the GPU.  The types,
 // the concurrency model and the other units of the host layer are in nw_host.h.
 #include <algorithm>
 
@@ -38,43 +39,24 @@ constexpr size_t kGroupMinSigs = 16384;
 constexpr size_t kGroupMinSigsPerKey = 4;
 static_assert(kStagedMaxSigs <= kGroupMinSigs, "staged calls never group");
 
-// One run of the certificate pipeline.  Every pointer is device memory except zseed; fields left
-// unset are null / zero.
-struct CertCall {
-    // inputs: certificate vote ranges, signatures, signer slots and the messages, either one 32-byte
-    // message per certificate (cert_msg32) or one per signature (msg_base / msg_off / msg_len)
-    size_t ncerts = 0, nsigs = 0;
-    const uint32_t *first = nullptr, *nv = nullptr, *signer = nullptr;
-    const uint8_t *sig = nullptr, *cert_msg32 = nullptr, *msg_base = nullptr;
-    const uint64_t *msg_off = nullptr, *msg_len = nullptr;
-    // options
-    const uint8_t* zseed = nullptr;   // host, 32 bytes; null: a strict-only call draws no coefficients
-    uint64_t cert_base = 0;
-    uint32_t batch_mode = 0;          // 0: strict verdicts only (sig_ok straight from k_finish)
-    const PreStaged* pre = nullptr;   // preamble state already in device memory (small host-buffer calls)
-    bool sync_check = false;          // wait for the device input check: NW_ERR_ARG before anything else runs
-    // outputs
-    uint8_t *cert_ok = nullptr, *sig_ok = nullptr;
-    uint32_t *flags = nullptr, *status = nullptr;   // flags null: workspace scratch
-    uint64_t* stake = nullptr;
-};
+}  // namespace
 
-// Enqueue the certificate pipeline on st (shared key lock held, workspace bound to st).
-int enqueue_certs(nw_ctx* ctx, Workspace* ws, const CertCall& c, hipStream_t st) {
-    const size_t ncerts = c.ncerts, nsigs = c.nsigs;
-    const int msgmode = c.msg_base ? 1 : 0;
-    const PreStaged* pre = c.pre;
-    uint32_t* d_flags = c.flags;
-    uint32_t* d_status = c.status;
-    if (!d_flags) {
-        NW_TRY(ws->ensure(ws->w_flags, nsigs * 4 + 4), "ws flags");
-        d_flags = ws->w_flags.as<uint32_t>();
-    }
+namespace nw {
+
+// signer grouping (device counting sort) when keys repeat
+static bool groups_signers(const nw_ctx* ctx, bool prestaged, size_t nsigs) {
+    return NW_GROUP_SIGNERS && !prestaged && nsigs >= kGroupMinSigs && ctx->nkeys > 1 &&
+           nsigs >= kGroupMinSigsPerKey * ctx->nkeys;
+}
+
+int reserve_certs(nw_ctx* ctx, Workspace* ws, size_t ncerts, size_t nsigs, uint32_t batch_mode, bool prestaged,
+                  bool own_flags) {
+    if (own_flags) NW_TRY(ws->ensure(ws->w_flags, nsigs * 4 + 4), "ws flags");
     NW_TRY(ws->ensure(ws->w_sig_cert, nsigs * 4 + 4), "ws sig_cert");
     NW_TRY(ws->ensure(ws->w_slow_count, 16), "ws slow_count");
     NW_TRY(ws->ensure(ws->w_slow_list, nsigs * 4 + 4), "ws slow_list");
     NW_TRY(ws->ensure(ws->w_slow_slot, nsigs * 4 + 4), "ws slow_slot");
-    if (c.batch_mode) {
+    if (batch_mode) {
         NW_TRY(ws->ensure(ws->w_slow_buf, nsigs * (size_t)SLOW_WORDS * 4 + 4), "ws slow_buf");
         NW_TRY(ws->ensure(ws->w_pslow, nsigs * (size_t)160 + 16), "ws pslow");
         NW_TRY(ws->ensure(ws->w_cert_state, ncerts * 4 + 16), "ws cert_state");
@@ -82,15 +64,24 @@ int enqueue_certs(nw_ctx* ctx, Workspace* ws, const CertCall& c, hipStream_t st)
     }
     NW_TRY(ws->ensure(ws->w_pbuf, nsigs * (size_t)PBUF_WORDS * 4 + 16), "ws pbuf");
     NW_TRY(ws->ensure(ws->w_pre, nsigs * 40 + 16), "ws pre");
-    // signer grouping (device counting sort) when keys repeat
-    const bool group = NW_GROUP_SIGNERS && !pre && nsigs >= kGroupMinSigs && ctx->nkeys > 1 &&
-                       nsigs >= kGroupMinSigsPerKey * ctx->nkeys;
-    if (group) {
+    if (groups_signers(ctx, prestaged, nsigs)) {
         NW_TRY(ws->ensure(ws->w_counts, ctx->nkeys * 4 + 16), "ws counts");
         NW_TRY(ws->ensure(ws->w_cursor, ctx->nkeys * 4 + 16), "ws cursor");
         NW_TRY(ws->ensure(ws->w_perm, nsigs * 4 + 16), "ws perm");
         NW_TRY(ws->ensure(ws->w_pinfo, nsigs * 8 + 16), "ws pinfo");
     }
+    return NW_OK;
+}
+
+int enqueue_certs(nw_ctx* ctx, Workspace* ws, const CertCall& c, hipStream_t st) {
+    const size_t ncerts = c.ncerts, nsigs = c.nsigs;
+    const int msgmode = c.msg_base ? 1 : 0;
+    const PreStaged* pre = c.pre;
+    uint32_t* d_flags = c.flags;
+    uint32_t* d_status = c.status;
+    NW_RC(reserve_certs(ctx, ws, ncerts, nsigs, c.batch_mode, pre != nullptr, !d_flags));
+    if (!d_flags) d_flags = ws->w_flags.as<uint32_t>();
+    const bool group = groups_signers(ctx, pre != nullptr, nsigs);
     uint32_t* sig_cert = pre ? pre->sig_cert : ws->w_sig_cert.as<uint32_t>();
     uint32_t* slow_count = pre ? pre->zero4 : ws->w_slow_count.as<uint32_t>();
     uint32_t* cert_state = !c.batch_mode ? nullptr : (pre ? pre->cert_state : ws->w_cert_state.as<uint32_t>());
@@ -211,6 +202,10 @@ int enqueue_certs(nw_ctx* ctx, Workspace* ws, const CertCall& c, hipStream_t st)
     NW_TRY(launch_finalize(fp, st), "k_cert_finalize / k_cert_exact");
     return NW_OK;
 }
+
+}  // namespace nw
+
+namespace {
 
 // Strict verify of signatures whose keys are not cached: k_verify_var + k_finish (messages, sigs
 // and raw keys already uploaded to the workspace).

@@ -1,0 +1,179 @@
+// The fourth launch pipeline of libnwcrypto: the crypto of a decoded mixed Core batch
+// (nw_core_batch_verify, include/nwcrypto.h; the batch is nw_corebatch.h, decoded by nw_primary.cpp)
+// as ONE stream-ordered submission.  Per call the stream carries, in this order:
+//   1. one H2D copy of the staged input block (CoreLayout::in)
+//   2. k_sha512_many            every digest preimage -> [D][64] digests
+//   3. k_core_link              digests -> the strict pass's messages, the certificate messages
+//   4. strict pass              enqueue_certs, batch_mode 0: every header, vote and
+//                               certificate-header signature -> one verdict byte each
+//   5. certificate pass         enqueue_certs, batch_mode 1: the votes of the certificates that enter
+//                               the batch step -> one verdict byte per certificate
+//   6. k_core_verdict           id check + fold -> n int32 verdicts
+//   7. one D2H copy of the verdicts, then one stream synchronization
+// Nothing the host does in the three-submission form (nw_cert_batch_verify) between its submissions
+// is needed for the next kernel to start: the digest is the signature's message, so it is read from
+// device memory, and the id comparison and the error precedence only decide the final verdict.
+#include <algorithm>
+
+#include "nw_corebatch.h"
+#include "nw_corebatch_kernels.h"
+#include "nw_host.h"
+
+using namespace nw;
+
+extern "C" {
+
+int nw_core_batch_verify(nw_ctx* ctx, const nw_core_batch* b, const uint8_t zseed[32], uint64_t cert_base,
+                         int32_t* verdict, uint64_t* certs_used) {
+    if (!b || (!verdict && !b->msgs.empty())) return NW_ERR_ARG;
+    if (!zseed) {
+        set_error(ctx, "zseed is NULL: batch coefficients need a fresh 32-byte CSPRNG seed per call");
+        return NW_ERR_ARG;
+    }
+    const size_t n = b->msgs.size(), D = b->dig_off.size(), H = b->ids.size() / 32, S = b->smember.size(),
+                 C = b->cnv.size(), V = b->cert_votes;
+    if (certs_used) *certs_used = C;
+    if (b->pending == 0) {   // the host decided every message: nothing to launch, no device needed
+        for (size_t i = 0; i < n; ++i) verdict[i] = b->desc[i].status;
+        return NW_OK;
+    }
+    if (!ctx) return NW_ERR_ARG;
+    if (n > 0xFFFFFFF0u || D > 0xFFFFFFF0u || S + C > 0xFFFFFFF0u || V > 0xFFFFFFF0u) return NW_ERR_ARG;
+    // Committee keys go to the key cache first (nw_committee_load takes the key lock exclusively, so
+    // before this call takes it shared); cached keys keep their slots.
+    std::vector<uint32_t> slot(b->names.size());
+    if ((S || C) && !b->names.empty())
+        NW_RC(nw_committee_load(ctx, reinterpret_cast<const uint8_t(*)[32]>(b->names.data()), b->stakes.data(),
+                                b->names.size(), slot.data()));
+    HostCall call(ctx);
+    NW_RC(call.begin());
+    Workspace* ws = call.ws;
+    hipStream_t st = call.st;
+    const CoreLayout l(n, D, b->pre.size(), H, S, C, V);
+    NW_TRY(ws->ensure(ws->w_io, l.device_bytes()), "ws io");
+    NW_TRY(ws->h_io.ensure(l.pinned_bytes()), "pinned io");
+    // every scratch buffer at the size of the larger pass, before the first launch
+    if (S) NW_RC(reserve_certs(ctx, ws, 1, S, 0, l.s_staged, true));
+    if (C) NW_RC(reserve_certs(ctx, ws, C, V, 1, l.c_staged, true));
+    // one staging pass over the struct of arrays
+    uint8_t* h = ws->h_io.bytes();
+    uint8_t* d_in = ws->w_io.as<uint8_t>();
+    uint8_t* d_work = d_in + l.work_at();
+    uint8_t* d_out = d_in + l.out_at();
+    auto put = [&](size_t at, const void* src, size_t bytes) {
+        if (bytes) std::memcpy(h + at, src, bytes);
+    };
+    put(l.desc, b->desc.data(), n * sizeof(CoreDesc));
+    put(l.pre, b->pre.data(), b->pre.size());
+    std::memset(h + l.pre + b->pre.size(), 0, 8);
+    put(l.dig_off, b->dig_off.data(), D * 8);
+    put(l.dig_len, b->dig_len.data(), D * 8);
+    put(l.ids, b->ids.data(), H * 32);
+    put(l.ssig, b->ssig.data(), S * 64);
+    put(l.ssrc, b->ssrc.data(), S * 4);
+    uint32_t* sslot = reinterpret_cast<uint32_t*>(h + l.sslot);
+    for (size_t s = 0; s < S; ++s) sslot[s] = slot[b->smember[s]];
+    uint32_t* sfn = reinterpret_cast<uint32_t*>(h + l.sfn);
+    sfn[0] = 0;
+    sfn[1] = (uint32_t)S;
+    uint32_t* cfirst = reinterpret_cast<uint32_t*>(h + l.cfirst);
+    uint32_t* vslot = reinterpret_cast<uint32_t*>(h + l.vslot);
+    put(l.cnv, b->cnv.data(), C * 4);
+    put(l.csrc, b->csrc.data(), C * 4);
+    size_t v0 = 0;
+    for (size_t c = 0; c < C; ++c) {
+        const size_t from = b->cvote0[c], nv = b->cnv[c];
+        cfirst[c] = (uint32_t)v0;
+        put(l.vsig + v0 * 64, b->vote_sig.data() + from * 64, nv * 64);
+        for (size_t v = 0; v < nv; ++v) vslot[v0 + v] = slot[b->vote_member[from + v]];
+        v0 += nv;
+    }
+    if (l.s_staged) prestage(h + l.spre, l.spl, sfn, sfn + 1, 1, S);
+    if (l.c_staged) prestage(h + l.cpre, l.cpl, cfirst, b->cnv.data(), C, V);
+    const PreStaged spre(d_in + l.spre, l.spl), cpre(d_in + l.cpre, l.cpl);
+    // 1. the whole input block
+    NW_TRY(hipMemcpyAsync(d_in, h, l.in.end, hipMemcpyHostToDevice, st), "H2D core batch");
+    // 2. digests
+    NW_TRY(launch_sha512_many((uint32_t)D, d_in + l.pre, reinterpret_cast<const uint64_t*>(d_in + l.dig_off),
+                              reinterpret_cast<const uint64_t*>(d_in + l.dig_len), d_work + l.dig, st),
+           "k_sha512_many");
+    // 3. digests -> messages of the two passes
+    CoreLinkParams lp{};
+    lp.nstrict = (uint32_t)S;
+    lp.ncerts = (uint32_t)C;
+    lp.ndig = (uint32_t)D;
+    lp.dig = d_work + l.dig;
+    lp.ssrc = reinterpret_cast<const uint32_t*>(d_in + l.ssrc);
+    lp.csrc = reinterpret_cast<const uint32_t*>(d_in + l.csrc);
+    lp.smsg = d_work + l.smsg;
+    lp.smsg_off = reinterpret_cast<uint64_t*>(d_work + l.smsg_off);
+    lp.smsg_len = reinterpret_cast<uint64_t*>(d_work + l.smsg_len);
+    lp.cmsg = d_work + l.cmsg;
+    NW_TRY(launch_core_link(lp, st), "k_core_link");
+    // 4. strict pass: all S signatures in one "certificate", per-signature messages
+    if (S) {
+        CertCall cc;
+        cc.ncerts = 1;
+        cc.nsigs = S;
+        cc.first = reinterpret_cast<const uint32_t*>(d_in + l.sfn);
+        cc.nv = cc.first + 1;
+        cc.sig = d_in + l.ssig;
+        cc.signer = reinterpret_cast<const uint32_t*>(d_in + l.sslot);
+        cc.msg_base = lp.smsg;
+        cc.msg_off = lp.smsg_off;
+        cc.msg_len = lp.smsg_len;
+        cc.batch_mode = 0;
+        cc.pre = l.s_staged ? &spre : nullptr;
+        cc.sig_ok = d_work + l.sok;
+        NW_RC(enqueue_certs(ctx, ws, cc, st));
+    }
+    // 5. certificate pass: certificate j draws its coefficients at batch index cert_base + j
+    if (C) {
+        CertCall cc;
+        cc.ncerts = C;
+        cc.nsigs = V;
+        cc.first = reinterpret_cast<const uint32_t*>(d_in + l.cfirst);
+        cc.nv = reinterpret_cast<const uint32_t*>(d_in + l.cnv);
+        cc.sig = d_in + l.vsig;
+        cc.signer = reinterpret_cast<const uint32_t*>(d_in + l.vslot);
+        cc.cert_msg32 = lp.cmsg;
+        cc.zseed = zseed;
+        cc.cert_base = cert_base;
+        cc.batch_mode = 1;
+        cc.pre = l.c_staged ? &cpre : nullptr;
+        cc.cert_ok = d_work + l.cok;
+        NW_RC(enqueue_certs(ctx, ws, cc, st));
+    }
+    // 6. verdicts
+    CoreVerdictParams vp{};
+    vp.n = (uint32_t)n;
+    vp.ndig = (uint32_t)D;
+    vp.nids = (uint32_t)H;
+    vp.nstrict = (uint32_t)S;
+    vp.ncerts = (uint32_t)C;
+    vp.desc = reinterpret_cast<const CoreDesc*>(d_in + l.desc);
+    vp.dig = d_work + l.dig;
+    vp.ids = d_in + l.ids;
+    vp.strict_ok = d_work + l.sok;
+    vp.cert_ok = d_work + l.cok;
+    vp.verdict = reinterpret_cast<int32_t*>(d_out + l.verdict);
+    NW_TRY(launch_core_verdict(vp, st), "k_core_verdict");
+    // 7. the H2D above has completed in stream order before this copy overwrites the staging buffer
+    NW_TRY(hipMemcpyAsync(h, d_out + l.verdict, n * 4, hipMemcpyDeviceToHost, st), "D2H verdicts");
+    NW_RC(call.finish());
+    std::memcpy(verdict, h, n * 4);
+    return NW_OK;
+}
+
+int nw_core_messages_verify(nw_ctx* ctx, const nw_committee* cm, const nw_core_state* state, const uint8_t* const* frame,
+                            const size_t* len, size_t n, const uint8_t zseed[32], uint64_t cert_base, int32_t* verdict,
+                            uint64_t* certs_used) {
+    nw_core_batch* b = nullptr;
+    int rc = nw_core_batch_decode(cm, state, frame, len, n, &b);
+    if (rc != NW_OK) return rc;
+    rc = nw_core_batch_verify(ctx, b, zseed, cert_base, verdict, certs_used);
+    nw_core_batch_free(b);
+    return rc;
+}
+
+}  // extern "C"

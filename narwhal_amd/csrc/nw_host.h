@@ -3,6 +3,7 @@
 //   nw_keycache.cpp   key cache, HBM budget, basepoint-table registry, context create/destroy
 //   nw_staging.cpp    pinned staging (Stager, chunked uploads, message and signature uploads)
 //   nw_api.cpp        the three pipelines and the entry points
+//   nw_corepipe.cpp   the mixed Core batch: digests, both signature passes and the verdicts in one submission
 // The pure host arithmetic (layouts, plans) is nw_host_plan.h.
 //
 // Concurrency model (the worker calls from 64 rayon threads,
@@ -272,6 +273,34 @@ private:
     std::shared_lock<std::shared_mutex> keys_;   // released after the lease
     std::optional<Lease> lease_;
 };
+
+// One run of the certificate pipeline (nw_api.cpp).  Every pointer is device memory except zseed;
+// fields left unset are null / zero.
+struct CertCall {
+    // inputs: certificate vote ranges, signatures, signer slots and the messages, either one 32-byte
+    // message per certificate (cert_msg32) or one per signature (msg_base / msg_off / msg_len)
+    size_t ncerts = 0, nsigs = 0;
+    const uint32_t *first = nullptr, *nv = nullptr, *signer = nullptr;
+    const uint8_t *sig = nullptr, *cert_msg32 = nullptr, *msg_base = nullptr;
+    const uint64_t *msg_off = nullptr, *msg_len = nullptr;
+    // options
+    const uint8_t* zseed = nullptr;   // host, 32 bytes; null: a strict-only call draws no coefficients
+    uint64_t cert_base = 0;
+    uint32_t batch_mode = 0;          // 0: strict verdicts only (sig_ok straight from k_finish)
+    const PreStaged* pre = nullptr;   // preamble state already in device memory (small host-buffer calls)
+    bool sync_check = false;          // wait for the device input check: NW_ERR_ARG before anything else runs
+    // outputs
+    uint8_t *cert_ok = nullptr, *sig_ok = nullptr;
+    uint32_t *flags = nullptr, *status = nullptr;   // flags null: workspace scratch
+    uint64_t* stake = nullptr;
+};
+// Enqueue the certificate pipeline on st (shared key lock held, workspace bound to st).
+int enqueue_certs(nw_ctx* ctx, Workspace* ws, const CertCall& c, hipStream_t st);
+// Grow the workspace scratch that a run over (ncerts, nsigs) takes (enqueue_certs does this for
+// itself).  A call that enqueues several runs on one stream reserves for all of them before its
+// first launch, so no buffer is reallocated under a kernel still in flight.
+int reserve_certs(nw_ctx* ctx, Workspace* ws, size_t ncerts, size_t nsigs, uint32_t batch_mode, bool prestaged,
+                  bool own_flags);
 
 // Wait for every call that may still read the key tables (exclusive key lock held).
 int drain_all(nw_ctx* ctx);

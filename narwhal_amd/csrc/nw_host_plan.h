@@ -113,6 +113,38 @@ struct CertsLayout {
           ok(out.take(nsigs)) {}
 };
 
+// Device block of a mixed Core batch (nw_core_batch_verify): n messages, D digests over ``pre_bytes``
+// of packed preimages, H claimed header ids, S strict signatures, C certificates with V votes.
+//   in    one staged H2D: descriptors, preimages + their offsets / lengths, claimed ids, the strict
+//         records (signature, key-cache slot, source digest, the (0, S) range pair), the certificate
+//         records (vote range, source digest), the votes (signature, slot), and the preamble state of
+//         each pass that carries it (spl: the strict pass, one "certificate" of S; cpl: the
+//         certificate pass)
+//   work  device only, behind ``in``: the digests, the strict pass's messages with their offsets and
+//         lengths, the certificate messages, the verdict bytes of both passes
+//   out   behind ``work``: the n int32 verdicts (one D2H)
+// Every segment is 256-byte aligned, so every 32-byte value in it is 32-byte aligned.
+struct CoreLayout {
+    bool s_staged, c_staged;
+    PreLayout spl, cpl;
+    Bump in, work, out;
+    size_t desc, pre, dig_off, dig_len, ids, ssig, sslot, ssrc, sfn, cfirst, cnv, csrc, vsig, vslot, spre, cpre;
+    size_t dig, smsg, smsg_off, smsg_len, cmsg, sok, cok;
+    size_t verdict;
+    CoreLayout(size_t n, size_t D, size_t pre_bytes, size_t H, size_t S, size_t C, size_t V)
+        : s_staged(S > 0 && S <= kStagedMaxSigs), c_staged(C > 0 && V <= kStagedMaxSigs), spl(S, 1), cpl(V, C),
+          desc(in.take(n * 32)), pre(in.take(pre_bytes + 8)), dig_off(in.take(D * 8)), dig_len(in.take(D * 8)),
+          ids(in.take(H * 32)), ssig(in.take(S * 64)), sslot(in.take(S * 4)), ssrc(in.take(S * 4)), sfn(in.take(8)),
+          cfirst(in.take(C * 4)), cnv(in.take(C * 4)), csrc(in.take(C * 4)), vsig(in.take(V * 64)),
+          vslot(in.take(V * 4)), spre(in.take(s_staged ? spl.bytes() : 0)), cpre(in.take(c_staged ? cpl.bytes() : 0)),
+          dig(work.take(D * 64)), smsg(work.take(S * 32 + 8)), smsg_off(work.take(S * 8)), smsg_len(work.take(S * 8)),
+          cmsg(work.take(C * 32)), sok(work.take(S)), cok(work.take(C)), verdict(out.take(n * 4)) {}
+    size_t work_at() const { return in.end; }              // device offsets of the other two blocks
+    size_t out_at() const { return in.end + work.end; }
+    size_t device_bytes() const { return in.end + work.end + out.end; }
+    size_t pinned_bytes() const { return std::max(in.end, out.end); }
+};
+
 // Staged block of per-signature messages (upload_messages): the packed bytes, offsets, lengths.
 struct MessageLayout {
     Bump b;

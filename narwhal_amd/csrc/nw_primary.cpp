@@ -15,6 +15,11 @@
 // with no per-vote objects: one nw_sha512_many (header ids and certificate digests), one
 // nw_verify_strict_many (header signatures), one nw_verify_certs (every vote of every certificate
 // that reached the batch step).  Nothing here computes a digest or a verdict on the CPU.
+//
+// The same reader also decodes mixed Core batches (nw_core_batch_decode, at the end of this file):
+// Header (variant 0), Vote (variant 1) and Certificate frames in arrival order, with every check of
+// Core::sanitize_* (primary/src/core.rs:306-346) that needs no crypto, into the struct of arrays of
+// nw_corebatch.h; their crypto is one submission (nw_core_batch_verify, nw_corepipe.cpp).
 #include <algorithm>
 #include <array>
 #include <cstring>
@@ -23,6 +28,7 @@
 #include <vector>
 
 #include "../../include/nwcrypto.h"
+#include "nw_corebatch.h"
 
 namespace {
 
@@ -141,7 +147,10 @@ namespace {
 // Header (primary/src/messages.rs:13-21) + its digest preimage (:70-84): author || round ||
 // (digest || worker_id)* || parents*, with the BTreeMap / BTreeSet semantics of the deserialized
 // containers (sorted, duplicate payload keys keep the last value, duplicate parents collapse).
-bool read_header(Reader& r, nw_cert_batch::Cert& c, std::vector<uint32_t>& workers, std::vector<uint8_t>& scratch) {
+// Fills the author, round, id, sig and header_pre fields of a nw_cert_batch::Cert or a
+// nw_core_batch::Msg.
+template <class Rec>
+bool read_header(Reader& r, Rec& c, std::vector<uint32_t>& workers, std::vector<uint8_t>& scratch) {
     if (!r.public_key(c.author, scratch)) return false;
     c.round = r.u64();
     const uint64_t np = r.u64();
@@ -202,43 +211,136 @@ bool read_header(Reader& r, nw_cert_batch::Cert& c, std::vector<uint32_t>& worke
     return true;
 }
 
+// Committee.authorities (config/src/lib.rs:161-177) indexed by name, for one decode call.
+struct CommitteeIndex {
+    const nw_committee* cm;
+    std::unordered_map<Key, uint32_t, KeyHash> member;
+    uint64_t quorum = 0;   // Committee::quorum_threshold (config/src/lib.rs:189-194)
+    CommitteeIndex(const nw_committee* c, std::vector<Key>& names, std::vector<uint32_t>& stakes) : cm(c) {
+        member.reserve(cm->n * 2);
+        names.resize(cm->n);
+        stakes.assign(cm->stake, cm->stake + cm->n);
+        uint64_t total = 0;
+        for (size_t i = 0; i < cm->n; ++i) {
+            std::memcpy(names[i].data(), cm->name[i], 32);
+            member.emplace(names[i], (uint32_t)i);
+            total += cm->stake[i];
+        }
+        quorum = 2 * total / 3 + 1;
+    }
+    uint64_t stake_of(const Key& k, uint32_t* idx) const {
+        auto it = member.find(k);
+        if (it == member.end()) return 0;
+        if (idx) *idx = it->second;
+        return cm->stake[it->second];
+    }
+    bool has_worker(uint32_t a, uint32_t w) const {   // Committee::worker (config/src/lib.rs:229-240)
+        if (!cm->worker_first || !cm->worker_id) return false;
+        for (uint32_t k = cm->worker_first[a]; k < cm->worker_first[a + 1]; ++k)
+            if (cm->worker_id[k] == w) return true;
+        return false;
+    }
+    // Header::verify after the id check: author stake, then every payload worker id.
+    int32_t header_error(const Key& author, const std::vector<uint32_t>& workers) const {
+        uint32_t aidx = 0;
+        if (stake_of(author, &aidx) == 0) return NW_DAG_UNKNOWN_AUTHORITY;
+        for (uint32_t w : workers)
+            if (!has_worker(aidx, w)) return NW_DAG_MALFORMED_HEADER;
+        return NW_DAG_OK;
+    }
+};
+
+struct DecodeScratch {
+    std::vector<uint8_t> b64;
+    std::vector<uint32_t> workers, used;
+};
+
+// A Certificate (primary/src/messages.rs:168-172) after the variant tag, and the host checks of
+// Certificate::verify: fills record c of batch b (a nw_cert_batch or a nw_core_batch: the votes go
+// to b's vote arrays) and sets c.status to SERIALIZATION, OK (genesis) or leaves it PENDING with
+// header_error / quorum_error set.
+template <class Batch, class Rec>
+void read_certificate(Reader& r, const CommitteeIndex& ci, Batch* b, Rec& c, DecodeScratch& t) {
+    if (!read_header(r, c, t.workers, t.b64)) {
+        c.status = NW_DAG_SERIALIZATION;
+        return;
+    }
+    const uint64_t nv = r.u64();
+    if (!r.ok || nv > (r.n - r.at) / 72) {   // each vote takes >= 8 + 64 bytes
+        c.status = NW_DAG_SERIALIZATION;
+        return;
+    }
+    const size_t v0 = b->vote_sig.size() / 64;
+    bool good = true;
+    for (uint64_t v = 0; v < nv && good; ++v) {
+        Key k;
+        const uint8_t* s;
+        good = r.public_key(k, t.b64) && r.take(64, &s);
+        if (good) {
+            b->vote_pk.insert(b->vote_pk.end(), k.begin(), k.end());
+            b->vote_sig.insert(b->vote_sig.end(), s, s + 64);
+        }
+    }
+    if (!good) {   // drop this certificate's partial votes
+        b->vote_pk.resize(v0 * 32);
+        b->vote_sig.resize(v0 * 64);
+        c.status = NW_DAG_SERIALIZATION;
+        return;
+    }
+    // bincode::deserialize allows trailing bytes: nothing to check past the votes.
+    c.first_vote = (uint32_t)v0;
+    c.n_votes = (uint32_t)nv;
+    b->vote_member.resize(v0 + nv, 0);
+    // Certificate digest preimage (:226-234): header.id || round || origin.
+    std::memcpy(c.cert_pre, c.id, 32);
+    std::memcpy(c.cert_pre + 32, &c.round, 8);
+    std::memcpy(c.cert_pre + 40, c.author.data(), 32);
+    // Genesis (:191-193 with PartialEq at :249-256): same id, round and origin as a genesis
+    // certificate, i.e. id = Digest::default(), round 0, origin a committee member.
+    static const uint8_t zero[32] = {0};
+    if (c.round == 0 && std::memcmp(c.id, zero, 32) == 0 && ci.member.count(c.author)) {
+        c.status = NW_DAG_OK;
+        return;
+    }
+    c.header_error = ci.header_error(c.author, t.workers);
+    // Quorum (:199-211): reuse, unknown authority, then the 2f+1 threshold.
+    uint64_t weight = 0;
+    t.used.clear();
+    for (uint32_t v = 0; v < nv; ++v) {
+        Key k;
+        std::memcpy(k.data(), &b->vote_pk[(v0 + v) * 32], 32);
+        uint32_t idx = 0;
+        const uint64_t st = ci.stake_of(k, &idx);
+        if (st && std::find(t.used.begin(), t.used.end(), idx) != t.used.end()) {
+            c.quorum_error = NW_DAG_AUTHORITY_REUSE;
+            break;
+        }
+        if (st == 0) {   // only known names enter `used`, so an unknown name fails here first
+            c.quorum_error = NW_DAG_UNKNOWN_AUTHORITY;
+            break;
+        }
+        t.used.push_back(idx);
+        b->vote_member[v0 + v] = idx;
+        weight += st;
+    }
+    if (c.quorum_error == NW_DAG_OK && weight < ci.quorum) c.quorum_error = NW_DAG_REQUIRES_QUORUM;
+}
+
+bool committee_ok(const nw_committee* cm) { return cm && !(cm->n && (!cm->name || !cm->stake)); }
+
 }  // namespace
 
 extern "C" {
 
 int nw_cert_batch_decode(const nw_committee* cm, const uint8_t* const* frame, const size_t* len, size_t n,
                          nw_cert_batch** out) {
-    if (!out || !cm || (cm->n && (!cm->name || !cm->stake)) || (n && (!frame || !len))) return NW_ERR_ARG;
+    if (!out || !committee_ok(cm) || (n && (!frame || !len))) return NW_ERR_ARG;
     *out = nullptr;
     auto* b = new (std::nothrow) nw_cert_batch;
     if (!b) return NW_ERR_NOMEM;
-    std::unordered_map<Key, uint32_t, KeyHash> member;   // Committee.authorities (config/src/lib.rs:161-177)
-    member.reserve(cm->n * 2);
-    b->names.resize(cm->n);
-    b->stakes.assign(cm->stake, cm->stake + cm->n);
-    uint64_t total = 0;
-    for (size_t i = 0; i < cm->n; ++i) {
-        std::memcpy(b->names[i].data(), cm->name[i], 32);
-        member.emplace(b->names[i], (uint32_t)i);
-        total += cm->stake[i];
-    }
-    const uint64_t quorum = 2 * total / 3 + 1;   // Committee::quorum_threshold (config/src/lib.rs:189-194)
-    auto stake_of = [&](const Key& k, uint32_t* idx) -> uint64_t {
-        auto it = member.find(k);
-        if (it == member.end()) return 0;
-        if (idx) *idx = it->second;
-        return cm->stake[it->second];
-    };
-    auto has_worker = [&](uint32_t a, uint32_t w) {   // Committee::worker (config/src/lib.rs:229-240)
-        if (!cm->worker_first || !cm->worker_id) return false;
-        for (uint32_t k = cm->worker_first[a]; k < cm->worker_first[a + 1]; ++k)
-            if (cm->worker_id[k] == w) return true;
-        return false;
-    };
+    const CommitteeIndex ci(cm, b->names, b->stakes);
     b->certs.resize(n);
-    std::vector<uint8_t> scratch;
-    std::vector<uint32_t> workers;
-    std::vector<uint32_t> used;
+    DecodeScratch t;
     for (size_t i = 0; i < n; ++i) {
         auto& c = b->certs[i];
         if (!frame[i] && len[i]) {
@@ -255,80 +357,7 @@ int nw_cert_batch_decode(const nw_committee* cm, const uint8_t* const* frame, co
             c.status = NW_DAG_NOT_CERTIFICATE;
             continue;
         }
-        if (!read_header(r, c, workers, scratch)) {
-            c.status = NW_DAG_SERIALIZATION;
-            continue;
-        }
-        const uint64_t nv = r.u64();
-        if (!r.ok || nv > (r.n - r.at) / 72) {   // each vote takes >= 8 + 64 bytes
-            c.status = NW_DAG_SERIALIZATION;
-            continue;
-        }
-        const size_t v0 = b->vote_sig.size() / 64;
-        bool good = true;
-        for (uint64_t v = 0; v < nv && good; ++v) {
-            Key k;
-            const uint8_t* s;
-            good = r.public_key(k, scratch) && r.take(64, &s);
-            if (good) {
-                b->vote_pk.insert(b->vote_pk.end(), k.begin(), k.end());
-                b->vote_sig.insert(b->vote_sig.end(), s, s + 64);
-            }
-        }
-        if (!good) {   // drop this certificate's partial votes
-            b->vote_pk.resize(v0 * 32);
-            b->vote_sig.resize(v0 * 64);
-            c.status = NW_DAG_SERIALIZATION;
-            continue;
-        }
-        // bincode::deserialize allows trailing bytes: nothing to check past the votes.
-        c.first_vote = (uint32_t)v0;
-        c.n_votes = (uint32_t)nv;
-        b->vote_member.resize(v0 + nv, 0);
-        // Certificate digest preimage (:226-234): header.id || round || origin.
-        std::memcpy(c.cert_pre, c.id, 32);
-        std::memcpy(c.cert_pre + 32, &c.round, 8);
-        std::memcpy(c.cert_pre + 40, c.author.data(), 32);
-        // Genesis (:191-193 with PartialEq at :249-256): same id, round and origin as a genesis
-        // certificate, i.e. id = Digest::default(), round 0, origin a committee member.
-        static const uint8_t zero[32] = {0};
-        uint32_t aidx = 0;
-        const uint64_t astake = stake_of(c.author, &aidx);
-        if (c.round == 0 && std::memcmp(c.id, zero, 32) == 0 && member.count(c.author)) {
-            c.status = NW_DAG_OK;
-            continue;
-        }
-        // Header::verify after the id check: author stake, then every payload worker id.
-        if (astake == 0) {
-            c.header_error = NW_DAG_UNKNOWN_AUTHORITY;
-        } else {
-            for (uint32_t w : workers)
-                if (!has_worker(aidx, w)) {
-                    c.header_error = NW_DAG_MALFORMED_HEADER;
-                    break;
-                }
-        }
-        // Quorum (:199-211): reuse, unknown authority, then the 2f+1 threshold.
-        uint64_t weight = 0;
-        used.clear();
-        for (uint32_t v = 0; v < nv; ++v) {
-            Key k;
-            std::memcpy(k.data(), &b->vote_pk[(v0 + v) * 32], 32);
-            uint32_t idx = 0;
-            const uint64_t st = stake_of(k, &idx);
-            if (st && std::find(used.begin(), used.end(), idx) != used.end()) {
-                c.quorum_error = NW_DAG_AUTHORITY_REUSE;
-                break;
-            }
-            if (st == 0) {   // only known names enter `used`, so an unknown name fails here first
-                c.quorum_error = NW_DAG_UNKNOWN_AUTHORITY;
-                break;
-            }
-            used.push_back(idx);
-            b->vote_member[v0 + v] = idx;
-            weight += st;
-        }
-        if (c.quorum_error == NW_DAG_OK && weight < quorum) c.quorum_error = NW_DAG_REQUIRES_QUORUM;
+        read_certificate(r, ci, b, c, t);
     }
     *out = b;
     return NW_OK;
@@ -454,6 +483,212 @@ int nw_certificates_verify(nw_ctx* ctx, const nw_committee* cm, const uint8_t* c
     rc = nw_cert_batch_verify(ctx, b, zseed, cert_base, verdict);
     nw_cert_batch_free(b);
     return rc;
+}
+
+}  // extern "C"
+
+// ---- mixed Core batches (nw_core_batch_*): Header, Vote and Certificate frames in arrival order ----
+namespace {
+
+using Msg = nw_core_batch::Msg;
+
+// Append a digest preimage at a 16-byte aligned offset of ``to``.
+size_t pack(std::vector<uint8_t>& to, const uint8_t* p, size_t n) {
+    const size_t at = (to.size() + 15) & ~(size_t)15;
+    to.resize(at);
+    to.insert(to.end(), p, p + n);
+    return at;
+}
+
+// The message's preimage goes to the device block (hot) or stays with the host (view only).
+void keep_preimage(nw_core_batch* b, Msg& m, const uint8_t* p, size_t n, bool hot) {
+    m.has_pre = true;
+    m.hot = hot;
+    m.pre_len = n;
+    m.pre_off = pack(hot ? b->pre : b->cold, p, n);
+}
+
+uint32_t add_digest(nw_core_batch* b, size_t off, size_t len) {
+    b->dig_off.push_back(off);
+    b->dig_len.push_back(len);
+    return (uint32_t)(b->dig_off.size() - 1);
+}
+
+// Strict-signature record: signature, committee member, and the digest that is its message.
+uint32_t add_strict(nw_core_batch* b, const uint8_t* sig, uint32_t member, uint32_t src) {
+    b->ssig.insert(b->ssig.end(), sig, sig + 64);
+    b->smember.push_back(member);
+    b->ssrc.push_back(src);
+    return (uint32_t)(b->smember.size() - 1);
+}
+
+// A pending Header or Certificate: its header digest and claimed id always go up (the id check
+// comes first); its signature only when the host checks after the id passed.
+void add_header(nw_core_batch* b, const CommitteeIndex& ci, Msg& m, nw::CoreDesc& d) {
+    keep_preimage(b, m, m.header_pre.data(), m.header_pre.size(), true);
+    d.dig = add_digest(b, m.pre_off, m.pre_len);
+    d.id = (uint32_t)(b->ids.size() / 32);
+    b->ids.insert(b->ids.end(), m.id, m.id + 32);
+    if (m.header_error == NW_DAG_OK) {
+        uint32_t aidx = 0;
+        ci.stake_of(m.author, &aidx);
+        d.strict = add_strict(b, m.sig, aidx, d.dig);
+    }
+}
+
+// PrimaryMessage::CertificatesRequest(Vec<Digest>, PublicKey) (primary/src/primary.rs:33-38).
+bool read_certificates_request(Reader& r, DecodeScratch& t) {
+    const uint64_t nd = r.u64();
+    const uint8_t* p;
+    if (!r.ok || nd > (r.n - r.at) / 32 || !r.take((size_t)nd * 32, &p)) return false;
+    Key requestor;
+    return r.public_key(requestor, t.b64);
+}
+
+void decode_core_message(nw_core_batch* b, const CommitteeIndex& ci, const nw_core_state* st, Reader& r, Msg& m,
+                         nw::CoreDesc& d, DecodeScratch& t) {
+    const uint32_t tag = r.u32();
+    if (!r.ok || tag > 3) {
+        m.status = NW_DAG_SERIALIZATION;
+        return;
+    }
+    if (tag == 3) {
+        m.status = read_certificates_request(r, t) ? NW_DAG_NOT_CORE_MESSAGE : NW_DAG_SERIALIZATION;
+        return;
+    }
+    if (tag == 0) {   // Header: sanitize_header (core.rs:306-318)
+        if (!read_header(r, m, t.workers, t.b64)) {
+            m.status = NW_DAG_SERIALIZATION;
+            return;
+        }
+        m.kind = NW_CORE_HEADER;
+        m.origin = m.author;
+        if (st && st->gc_round > m.round) {
+            m.status = NW_DAG_TOO_OLD;
+            keep_preimage(b, m, m.header_pre.data(), m.header_pre.size(), false);
+            return;
+        }
+        m.header_error = ci.header_error(m.author, t.workers);
+        add_header(b, ci, m, d);
+        return;
+    }
+    if (tag == 1) {   // Vote (messages.rs:105-111): sanitize_vote (core.rs:320-336)
+        const uint8_t *id, *sig;
+        if (!r.take(32, &id)) {
+            m.status = NW_DAG_SERIALIZATION;
+            return;
+        }
+        const uint64_t round = r.u64();
+        Key origin, author;
+        if (!r.public_key(origin, t.b64) || !r.public_key(author, t.b64) || !r.take(64, &sig)) {
+            m.status = NW_DAG_SERIALIZATION;
+            return;
+        }
+        m.kind = NW_CORE_VOTE;
+        m.round = round;
+        m.origin = origin;
+        m.author = author;
+        std::memcpy(m.id, id, 32);
+        std::memcpy(m.sig, sig, 64);
+        uint8_t pre[72];   // Hash for Vote (:145-153): id || round || origin
+        std::memcpy(pre, id, 32);
+        std::memcpy(pre + 32, &round, 8);
+        std::memcpy(pre + 40, origin.data(), 32);
+        uint32_t aidx = 0;
+        if (st && st->round > round)
+            m.status = NW_DAG_TOO_OLD;
+        else if (st && !(std::memcmp(id, st->id, 32) == 0 && std::memcmp(origin.data(), st->author, 32) == 0 &&
+                         round == st->round))
+            m.status = NW_DAG_UNEXPECTED_VOTE;
+        else if (ci.stake_of(author, &aidx) == 0)   // Vote::verify (:133-136)
+            m.status = NW_DAG_UNKNOWN_AUTHORITY;
+        keep_preimage(b, m, pre, 72, m.status == NW_DAG_PENDING);
+        if (m.status == NW_DAG_PENDING) d.strict = add_strict(b, m.sig, aidx, add_digest(b, m.pre_off, 72));
+        return;
+    }
+    // Certificate: sanitize_certificate (core.rs:338-346)
+    read_certificate(r, ci, b, m, t);
+    if (m.status == NW_DAG_SERIALIZATION) return;
+    m.kind = NW_CORE_CERTIFICATE;
+    m.origin = m.author;
+    if (st && st->gc_round > m.round) m.status = NW_DAG_TOO_OLD;   // before the genesis shortcut
+    if (m.status != NW_DAG_PENDING) {
+        keep_preimage(b, m, m.header_pre.data(), m.header_pre.size(), false);
+        return;
+    }
+    add_header(b, ci, m, d);
+    if (m.header_error == NW_DAG_OK && m.quorum_error == NW_DAG_OK) {   // enters the batch step
+        d.cert = (uint32_t)b->cnv.size();
+        b->cvote0.push_back(m.first_vote);
+        b->cnv.push_back(m.n_votes);
+        b->csrc.push_back(add_digest(b, pack(b->pre, m.cert_pre, 72), 72));
+        b->cert_votes += m.n_votes;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int nw_core_batch_decode(const nw_committee* cm, const nw_core_state* st, const uint8_t* const* frame, const size_t* len,
+                         size_t n, nw_core_batch** out) {
+    if (!out || !committee_ok(cm) || (n && (!frame || !len))) return NW_ERR_ARG;
+    *out = nullptr;
+    for (size_t i = 0; i < n; ++i)
+        if (!frame[i] && len[i]) return NW_ERR_ARG;
+    auto* b = new (std::nothrow) nw_core_batch;
+    if (!b) return NW_ERR_NOMEM;
+    const CommitteeIndex ci(cm, b->names, b->stakes);
+    b->msgs.resize(n);
+    b->desc.resize(n);
+    DecodeScratch t;
+    for (size_t i = 0; i < n; ++i) {
+        Msg& m = b->msgs[i];
+        nw::CoreDesc& d = b->desc[i];
+        d.dig = d.id = d.strict = d.cert = nw::CORE_NO_INDEX;
+        Reader r{frame[i], len[i]};
+        decode_core_message(b, ci, st, r, m, d, t);
+        std::vector<uint8_t>().swap(m.header_pre);   // packed into pre / cold
+        d.status = m.status;
+        d.header_error = m.header_error;
+        d.quorum_error = m.quorum_error;
+        d.kind = (uint32_t)m.kind;
+        if (m.status == NW_DAG_PENDING) ++b->pending;
+    }
+    *out = b;
+    return NW_OK;
+}
+
+void nw_core_batch_free(nw_core_batch* b) { delete b; }
+
+size_t nw_core_batch_size(const nw_core_batch* b) { return b ? b->msgs.size() : 0; }
+
+int nw_core_batch_view(const nw_core_batch* b, size_t i, nw_core_view* out) {
+    if (!b || !out || i >= b->msgs.size()) return NW_ERR_ARG;
+    const Msg& m = b->msgs[i];
+    std::memset(out, 0, sizeof(*out));
+    out->kind = m.kind;
+    out->status = m.status;
+    out->header_error = m.header_error;
+    out->quorum_error = m.quorum_error;
+    if (m.kind == NW_CORE_OTHER) return NW_OK;
+    out->round = m.round;
+    out->author = m.author.data();
+    out->id = m.id;
+    out->origin = m.origin.data();
+    out->signature = m.sig;
+    if (m.has_pre) {
+        out->preimage = (m.hot ? b->pre : b->cold).data() + m.pre_off;
+        out->preimage_len = m.pre_len;
+    }
+    if (m.kind == NW_CORE_CERTIFICATE) {
+        out->cert_preimage = m.cert_pre;
+        out->first_vote = m.first_vote;
+        out->n_votes = m.n_votes;
+        out->vote_keys = b->vote_pk.data() + (size_t)m.first_vote * 32;
+        out->vote_sigs = b->vote_sig.data() + (size_t)m.first_vote * 64;
+    }
+    return NW_OK;
 }
 
 }  // extern "C"
