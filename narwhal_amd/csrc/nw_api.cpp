@@ -25,81 +25,30 @@ struct nw_job {
     }
 };
 
-namespace {
-
-// Signer grouping on (1, release) or off (0: variant builds for the A/B of the grouping itself).
-#ifndef NW_GROUP_SIGNERS
-#define NW_GROUP_SIGNERS 1
-#endif
-// Group signatures by signer (key-table locality) above this batch size, and only when keys repeat
-// (at least kGroupMinSigsPerKey signatures per cached key on average): the worker's load (62,500
-// signatures over 100,000 keys, each key at most once) gains nothing from the order and would pay
-// the 100,000-slot scan (0.16 ms of a 0.47 ms batch, profiles/r02/kernel_stats_w_r02.csv).
-constexpr size_t kGroupMinSigs = 16384;
-constexpr size_t kGroupMinSigsPerKey = 4;
-static_assert(kStagedMaxSigs <= kGroupMinSigs, "staged calls never group");
-
-}  // namespace
-
 namespace nw {
 
-// signer grouping (device counting sort) when keys repeat
-static bool groups_signers(const nw_ctx* ctx, bool prestaged, size_t nsigs) {
-    return NW_GROUP_SIGNERS && !prestaged && nsigs >= kGroupMinSigs && ctx->nkeys > 1 &&
-           nsigs >= kGroupMinSigsPerKey * ctx->nkeys;
-}
-
-int reserve_certs(nw_ctx* ctx, Workspace* ws, size_t ncerts, size_t nsigs, uint32_t batch_mode, bool prestaged,
-                  bool own_flags) {
-    if (own_flags) NW_TRY(ws->ensure(ws->w_flags, nsigs * 4 + 4), "ws flags");
-    NW_TRY(ws->ensure(ws->w_sig_cert, nsigs * 4 + 4), "ws sig_cert");
-    NW_TRY(ws->ensure(ws->w_slow_count, 16), "ws slow_count");
-    NW_TRY(ws->ensure(ws->w_slow_list, nsigs * 4 + 4), "ws slow_list");
-    NW_TRY(ws->ensure(ws->w_slow_slot, nsigs * 4 + 4), "ws slow_slot");
-    if (batch_mode) {
-        NW_TRY(ws->ensure(ws->w_slow_buf, nsigs * (size_t)SLOW_WORDS * 4 + 4), "ws slow_buf");
-        NW_TRY(ws->ensure(ws->w_pslow, nsigs * (size_t)160 + 16), "ws pslow");
-        NW_TRY(ws->ensure(ws->w_cert_state, ncerts * 4 + 16), "ws cert_state");
-        NW_TRY(ws->ensure(ws->w_exact, ncerts * 4 + 16), "ws exact list");
-    }
-    NW_TRY(ws->ensure(ws->w_pbuf, nsigs * (size_t)PBUF_WORDS * 4 + 16), "ws pbuf");
-    NW_TRY(ws->ensure(ws->w_pre, nsigs * 40 + 16), "ws pre");
-    if (groups_signers(ctx, prestaged, nsigs)) {
-        NW_TRY(ws->ensure(ws->w_counts, ctx->nkeys * 4 + 16), "ws counts");
-        NW_TRY(ws->ensure(ws->w_cursor, ctx->nkeys * 4 + 16), "ws cursor");
-        NW_TRY(ws->ensure(ws->w_perm, nsigs * 4 + 16), "ws perm");
-        NW_TRY(ws->ensure(ws->w_pinfo, nsigs * 8 + 16), "ws pinfo");
-    }
-    return NW_OK;
-}
-
-int enqueue_certs(nw_ctx* ctx, Workspace* ws, const CertCall& c, hipStream_t st) {
+int enqueue_certs(nw_ctx* ctx, Workspace* ws, const CertCall& c, const CertScratch& s, hipStream_t st) {
     const size_t ncerts = c.ncerts, nsigs = c.nsigs;
     const int msgmode = c.msg_base ? 1 : 0;
     const PreStaged* pre = c.pre;
-    uint32_t* d_flags = c.flags;
+    auto at = [&](size_t off, bool have = true) {   // an absent segment (size 0) is a null pointer to the kernels
+        return have ? reinterpret_cast<uint32_t*>(ws->scratch.bytes() + off) : nullptr;
+    };
+    uint32_t* d_flags = c.flags ? c.flags : at(s.flags);
     uint32_t* d_status = c.status;
-    NW_RC(reserve_certs(ctx, ws, ncerts, nsigs, c.batch_mode, pre != nullptr, !d_flags));
-    if (!d_flags) d_flags = ws->w_flags.as<uint32_t>();
-    const bool group = groups_signers(ctx, pre != nullptr, nsigs);
-    uint32_t* sig_cert = pre ? pre->sig_cert : ws->w_sig_cert.as<uint32_t>();
-    uint32_t* slow_count = pre ? pre->zero4 : ws->w_slow_count.as<uint32_t>();
-    uint32_t* cert_state = !c.batch_mode ? nullptr : (pre ? pre->cert_state : ws->w_cert_state.as<uint32_t>());
+    uint32_t* sig_cert = pre ? pre->sig_cert : at(s.sig_cert);
+    uint32_t* slow_count = pre ? pre->zero4 : at(s.slow_count);
+    uint32_t* cert_state = !c.batch_mode ? nullptr : (pre ? pre->cert_state : at(s.cert_state));
     if (!pre) {
         // Preamble in two launches: sig_cert = NO_CERT, zero the slot counts, the slow-path counter,
         // the certificate states and the status word; expand certificates; histogram signer slots;
         // check the device inputs into the status word.  sync_check: the call waits for that check
         // and returns NW_ERR_ARG before anything else is enqueued.
-        if (c.sync_check) {
-            NW_TRY(ws->ensure(ws->w_status, 16), "ws status");
-            d_status = ws->w_status.as<uint32_t>();
-        }
+        if (c.sync_check) d_status = at(s.status);
         NW_TRY(launch_prep_expand((uint32_t)ncerts, (uint32_t)nsigs, (uint32_t)ctx->nkeys, c.first, c.nv, c.signer,
-                                  sig_cert, slow_count, group ? ws->w_counts.as<uint32_t>() : nullptr, d_status,
-                                  cert_state, st),
+                                  sig_cert, slow_count, at(s.counts, s.group), d_status, cert_state, st),
                "k_prep_certs / k_expand_count");
-        if (c.sync_check) {
-            NW_TRY(ws->h_io.ensure(16), "pinned status");
+        if (c.sync_check) {   // 16 bytes of h_io: reserved by the caller
             NW_TRY(hipMemcpyAsync(ws->h_io.p, d_status, 4, hipMemcpyDeviceToHost, st), "D2H status");
             NW_TRY(hipStreamSynchronize(st), "sync(status)");
             uint32_t sv = 0;
@@ -135,21 +84,20 @@ int enqueue_certs(nw_ctx* ctx, Workspace* ws, const CertCall& c, hipStream_t st)
     std::memcpy(vp.zseed, c.zseed ? c.zseed : kNoSeed, 32);
     vp.flags = d_flags;
     vp.slow_count = slow_count;
-    vp.slow_list = ws->w_slow_list.as<uint32_t>();
-    vp.slow_slot = ws->w_slow_slot.as<uint32_t>();
-    vp.slow_buf = ws->w_slow_buf.as<uint32_t>();
-    vp.pslow = c.batch_mode ? ws->w_pslow.as<uint32_t>() : nullptr;
+    vp.slow_list = at(s.slow_list);
+    vp.slow_slot = at(s.slow_slot);
+    vp.slow_buf = at(s.slow_buf, c.batch_mode);
+    vp.pslow = at(s.pslow, c.batch_mode);
     vp.cert_state = cert_state;
     vp.ok_out = c.batch_mode ? nullptr : c.sig_ok;
-    vp.pbuf = ws->w_pbuf.as<uint32_t>();
-    vp.pre = ws->w_pre.as<uint32_t>();
-    if (group) {
-        NW_TRY(launch_group_scatter((uint32_t)nsigs, (uint32_t)ctx->nkeys, c.signer, sig_cert,
-                                    ws->w_counts.as<uint32_t>(), ws->w_cursor.as<uint32_t>(), ws->w_perm.as<uint32_t>(),
-                                    ws->w_pinfo.as<uint2>(), st),
+    vp.pbuf = at(s.pbuf);
+    vp.pre = at(s.pre);
+    if (s.group) {
+        vp.perm = at(s.perm);
+        vp.pinfo = reinterpret_cast<const uint2*>(at(s.pinfo));
+        NW_TRY(launch_group_scatter((uint32_t)nsigs, (uint32_t)ctx->nkeys, c.signer, sig_cert, at(s.counts),
+                                    at(s.cursor), at(s.perm), reinterpret_cast<uint2*>(at(s.pinfo)), st),
                "signer grouping");
-        vp.perm = ws->w_perm.as<uint32_t>();
-        vp.pinfo = ws->w_pinfo.as<uint2>();
     }
     vp.gn = (uint32_t)nsigs;   // every column, from g0 = 0
     vp.fk = finish_k_for(ctx->finish_k, nsigs);
@@ -193,7 +141,7 @@ int enqueue_certs(nw_ctx* ctx, Workspace* ws, const CertCall& c, hipStream_t st)
     fp.accepted_stake = c.stake;
     fp.sig_ok = c.sig_ok;
     fp.exact_count = slow_count + 1;   // word 1 of the zeroed slow-path counter block
-    fp.exact_list = ws->w_exact.as<uint32_t>();
+    fp.exact_list = at(s.exact);
     if (slow_tail_fits(ncerts, nsigs)) {   // one header / vote batch: exact path + finalize in one launch
         NW_TRY(launch_slow_tail(vp, fp, msgmode, ctx->key_window, st), "k_slow_tail");
         return NW_OK;
@@ -207,66 +155,64 @@ int enqueue_certs(nw_ctx* ctx, Workspace* ws, const CertCall& c, hipStream_t st)
 
 namespace {
 
-// Strict verify of signatures whose keys are not cached: k_verify_var + k_finish (messages, sigs
-// and raw keys already uploaded to the workspace).
-int enqueue_strict_var(nw_ctx* ctx, Workspace* ws, size_t n, hipStream_t st, uint8_t* d_ok = nullptr) {
-    NW_TRY(ws->ensure(ws->w_flags, n * 4 + 4), "ws flags");
-    NW_TRY(ws->ensure(ws->w_sig_cert, n * 4 + 4), "ws sig_cert");
-    NW_TRY(ws->ensure(ws->w_pbuf, n * (size_t)PBUF_WORDS * 4 + 16), "ws pbuf");
-    NW_TRY(ws->ensure(ws->w_pre, n * 40 + 16), "ws pre");
-    NW_TRY(ws->ensure(ws->w_var, n * 320 * 4 + 16), "ws var table");
-    NW_TRY(hipMemsetAsync(ws->w_sig_cert.p, 0, n * 4 + 4, st), "memset sig_cert");
+// Strict verify of signatures whose keys are not cached: k_verify_var + k_finish over the uploaded
+// messages, sigs and raw keys (layout l at d_in) and the reserved scratch layout s.
+int enqueue_strict_var(nw_ctx* ctx, Workspace* ws, size_t n, const uint8_t* d_in, const SigKeysLayout& l,
+                       const VarScratch& s, hipStream_t st, uint8_t* d_ok) {
+    auto at = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws->scratch.bytes() + off); };
+    NW_TRY(hipMemsetAsync(at(s.sig_cert), 0, n * 4 + 4, st), "memset sig_cert");
     VerifyParams vp{};
     vp.n = (uint32_t)n;
     vp.gn = (uint32_t)n;
     vp.fk = finish_k_for(ctx->finish_k, n);
-    vp.sig = ws->w_sig.as<uint8_t>();
-    vp.sig_keys = ws->w_keys.as<uint32_t>();
-    vp.sig_cert = ws->w_sig_cert.as<uint32_t>();
-    vp.msg_base = ws->w_msg.as<uint8_t>();
-    vp.msg_off = ws->w_msg_off.as<uint64_t>();
-    vp.msg_len = ws->w_msg_len.as<uint64_t>();
+    vp.sig = d_in + l.sig;
+    vp.sig_keys = reinterpret_cast<const uint32_t*>(d_in + l.keys);
+    vp.sig_cert = at(s.sig_cert);
+    vp.msg_base = d_in + l.msgs + l.ml.packed;
+    vp.msg_off = reinterpret_cast<const uint64_t*>(d_in + l.msgs + l.ml.off);
+    vp.msg_len = reinterpret_cast<const uint64_t*>(d_in + l.msgs + l.ml.len);
     vp.btab = ctx->d_btab;
-    vp.flags = ws->w_flags.as<uint32_t>();
-    vp.pbuf = ws->w_pbuf.as<uint32_t>();
-    vp.pre = ws->w_pre.as<uint32_t>();
+    vp.flags = at(s.flags);
+    vp.pbuf = at(s.pbuf);
+    vp.pre = at(s.pre);
     vp.ok_out = d_ok;   // verdict bytes straight from k_finish
-    NW_TRY(launch_verify_var(vp, 1, ws->w_var.as<uint32_t>(), st), "k_verify_var");
+    NW_TRY(launch_verify_var(vp, 1, at(s.var), st), "k_verify_var");
     NW_TRY(launch_finish(vp, st), "k_finish");
     return NW_OK;
 }
 
 // One randomized batch verify without the key cache (the Pippenger MSM of nw_msm.hip) of nb
-// consecutive batches, batch b = the next counts[b] signatures.  Messages, sigs and raw keys are in
-// the workspace.
+// consecutive batches, batch b = the next counts[b] signatures, as the body of a host-buffer call:
+// plan, the call's one reservation, the uploads, the launches.
 struct MsmCall {
-    size_t nb = 0;
+    size_t nb = 0, nsig = 0;
     const uint32_t* counts = nullptr;   // host
-    size_t nsig = 0;
-    uint64_t msg_flen = UINT64_MAX;     // see upload_messages
     const uint8_t* zseed = nullptr;     // host, 32 bytes
     uint64_t batch_base = 0;
     uint32_t z_off = 0;
-    // outputs (device)
-    uint8_t* batch_ok = nullptr;        // [nb] verdicts
-    uint32_t* point_out = nullptr;      // [nb][40] partial sums before the identity test
-    uint32_t** bad_out = nullptr;       // receives the device address of the [nb] parse/decode failure flags
+    bool partial = false;               // out: the [40]-word sum before the identity test, not the [nb] verdicts
+    uint8_t* out = nullptr;             // device results, set by run_msm
+    uint32_t* bad = nullptr;            // [nb] parse / decode failure flags
 };
 
-int enqueue_msm(nw_ctx* ctx, Workspace* ws, const MsmCall& c, hipStream_t st) {
-    const size_t nb = c.nb, nsig = c.nsig;
+int run_msm(nw_ctx* ctx, Workspace* ws, hipStream_t st, MsmCall& c, const uint8_t* const* msg, const size_t* len,
+            const uint8_t (*pk)[32], const uint8_t (*sig)[64]) {
+    const size_t nb = c.nb, nsig = c.nsig, total = message_bytes(len, nsig);
     const MsmPlan plan = msm_plan(c.counts, nb, nsig);
-    const MsmMetaLayout ml(nb, nsig, plan);
-    const size_t ntasks = plan.tasks.size(), B = (size_t)1 << (plan.C - 1);
-    NW_TRY(ws->ensure(ws->w_msm_meta, ml.bytes()), "ws msm meta");
-    NW_TRY(ws->ensure(ws->w_msm_ent, 2 * nsig * MSM_ENT_WORDS * 4 + 16), "ws msm entries");
-    NW_TRY(ws->ensure(ws->w_msm_dig, (size_t)plan.NA * 2 * nsig * 2 + 16), "ws msm digits");
-    NW_TRY(ws->ensure(ws->w_msm_zs, (size_t)MSM_ZS_WORDS * nsig * 4 + 16), "ws msm zs");
-    NW_TRY(ws->ensure(ws->w_msm_bkt, ntasks * B * MSM_PT_WORDS * 4 + 16), "ws msm buckets");
-    NW_TRY(ws->ensure(ws->w_msm_part, ntasks * 128 * MSM_PT_WORDS * 4 + 16), "ws msm partials");
-    NW_TRY(ws->ensure(ws->w_msm_wpart, (ntasks + nb * plan.NA) * MSM_PT_WORDS * 4 + 16), "ws msm window sums");
+    const MsmScratch s(nb, nsig, plan);
+    const MsmMetaLayout& ml = s.ml;
+    const size_t ntasks = plan.tasks.size();
+    const SigKeysLayout l(total, nsig);
+    Stager sg(ctx, ws, st);
+    NW_RC(sg.reserve(l.in.end, c.partial ? MSM_PT_WORDS * 4 + 16 : nb + 16, s.bytes(), ml.bytes()));
+    uint64_t msg_flen = UINT64_MAX;   // see upload_messages
+    NW_RC(upload_messages(sg, l.msgs, l.ml, msg, len, nsig, total, &msg_flen));
+    NW_RC(sg.put(l.sig, sig, nsig * 64, "H2D sig"));
+    NW_RC(sg.put(l.keys, pk, nsig * 32, "H2D keys"));
+    const uint8_t* d_in = sg.dev(0);
+    c.out = sg.dev(l.in.end);
+    auto at = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws->scratch.bytes() + off); };
     // staged in the workspace's second pinned buffer (every caller synchronizes before returning)
-    NW_TRY(ws->h_meta.ensure(ml.bytes()), "pinned msm meta");
     uint8_t* hmeta = ws->h_meta.bytes();
     std::memset(hmeta, 0, ml.bytes());
     std::memcpy(hmeta + ml.bfirst, plan.bfirst.data(), nb * 4);
@@ -274,7 +220,7 @@ int enqueue_msm(nw_ctx* ctx, Workspace* ws, const MsmCall& c, hipStream_t st) {
     if (nsig) std::memcpy(hmeta + ml.sig_batch, plan.sig_batch.data(), nsig * 4);
     std::memcpy(hmeta + ml.wfirst, plan.wfirst.data(), plan.wfirst.size() * 4);
     if (ntasks) std::memcpy(hmeta + ml.tasks, plan.tasks.data(), ntasks * sizeof(MsmTask));
-    uint8_t* dm = ws->w_msm_meta.as<uint8_t>();
+    uint8_t* dm = ws->scratch.bytes() + s.meta;
     NW_TRY(hipMemcpyAsync(dm, hmeta, ml.bytes(), hipMemcpyHostToDevice, st), "H2D msm meta");
     MsmParams mp{};
     mp.nb = (uint32_t)nb;
@@ -283,65 +229,61 @@ int enqueue_msm(nw_ctx* ctx, Workspace* ws, const MsmCall& c, hipStream_t st) {
     mp.bfirst = reinterpret_cast<const uint32_t*>(dm + ml.bfirst);
     mp.bcount = reinterpret_cast<const uint32_t*>(dm + ml.bcount);
     mp.sig_batch = reinterpret_cast<const uint32_t*>(dm + ml.sig_batch);
-    mp.sig = ws->w_sig.as<uint8_t>();
-    mp.keys = ws->w_keys.as<uint32_t>();
-    mp.msg_base = ws->w_msg.as<uint8_t>();
-    mp.msg_off = ws->w_msg_off.as<uint64_t>();
-    mp.msg_len = ws->w_msg_len.as<uint64_t>();
-    mp.msg_flen = c.msg_flen;
+    mp.sig = d_in + l.sig;
+    mp.keys = reinterpret_cast<const uint32_t*>(d_in + l.keys);
+    mp.msg_base = d_in + l.msgs + l.ml.packed;
+    mp.msg_off = reinterpret_cast<const uint64_t*>(d_in + l.msgs + l.ml.off);
+    mp.msg_len = reinterpret_cast<const uint64_t*>(d_in + l.msgs + l.ml.len);
+    mp.msg_flen = msg_flen;
     mp.batch_base = c.batch_base;
     mp.z_off = c.z_off;
     std::memcpy(mp.zseed, c.zseed, 32);
-    mp.ent = ws->w_msm_ent.as<uint32_t>();
-    mp.dig = ws->w_msm_dig.as<int16_t>();
-    mp.zs = ws->w_msm_zs.as<uint32_t>();
+    mp.ent = at(s.ent);
+    mp.dig = reinterpret_cast<int16_t*>(at(s.dig));
+    mp.zs = at(s.zs);
     mp.bad = reinterpret_cast<uint32_t*>(dm + ml.bad);
     mp.tasks = reinterpret_cast<const MsmTask*>(dm + ml.tasks);
     mp.ntasks = (uint32_t)ntasks;
-    mp.bkt = ws->w_msm_bkt.as<uint32_t>();
-    mp.part = ws->w_msm_part.as<uint32_t>();
-    mp.wpart = ws->w_msm_wpart.as<uint32_t>();
+    mp.bkt = at(s.bkt);
+    mp.part = at(s.part);
+    mp.wpart = at(s.wpart);
     mp.wfirst = reinterpret_cast<const uint32_t*>(dm + ml.wfirst);
     mp.one_task_windows = plan.one_task_windows;
     mp.btab = ctx->d_btab;
-    mp.batch_ok = c.batch_ok;
-    mp.point_out = c.point_out;
+    mp.batch_ok = c.partial ? nullptr : c.out;
+    mp.point_out = c.partial ? reinterpret_cast<uint32_t*>(c.out) : nullptr;
     NW_TRY(launch_msm(mp, st), "k_msm");
-    if (c.bad_out) *c.bad_out = mp.bad;
+    c.bad = mp.bad;
     return NW_OK;
 }
 
 // The certificate pipeline over host buffers with per-signature messages, staged segment by segment
 // (nw_verify_batches; run_generic's large calls are its one batch [0, n)).  cc carries the counts
-// and the options; the verdicts land in ws->w_cert_ok and, with want_sig_ok, ws->w_ok.
-int enqueue_staged(nw_ctx* ctx, Workspace* ws, hipStream_t st, CertCall cc, const uint32_t* first, const uint32_t* nv,
+// and the options and receives the device addresses (verdicts at cc.cert_ok / cc.sig_ok).
+int enqueue_staged(nw_ctx* ctx, Workspace* ws, hipStream_t st, CertCall& cc, const uint32_t* first, const uint32_t* nv,
                    const uint8_t* const* msg, const size_t* len, const uint32_t* signer, const uint8_t (*sig)[64],
                    bool want_sig_ok) {
     const size_t nb = cc.ncerts, nsigs = cc.nsigs, total = message_bytes(len, nsigs);
+    const CertScratch cs = cert_scratch(ctx, nb, nsigs, cc.batch_mode, false, true);
+    const StagedLayout l(total, nsigs, nb);
     Stager sg(ctx, ws, st);
-    NW_RC(sg.reserve(MessageLayout(total, nsigs).bytes() + Stager::room(nsigs * 64) + Stager::room(nsigs * 4) +
-                     2 * Stager::room(nb * 4)));
-    NW_RC(upload_messages(ctx, ws, sg, msg, len, nsigs, total));
-    NW_TRY(ws->ensure(ws->w_sig, nsigs * 64 + 64), "ws sig");
-    NW_TRY(ws->ensure(ws->w_signer, nsigs * 4 + 4), "ws signer");
-    NW_TRY(ws->ensure(ws->w_cert_first, nb * 4 + 4), "ws first");
-    NW_TRY(ws->ensure(ws->w_cert_n, nb * 4 + 4), "ws n");
-    NW_TRY(ws->ensure(ws->w_cert_ok, nb + 16), "ws cert_ok");
-    NW_TRY(ws->ensure(ws->w_ok, nsigs + 16), "ws ok");
-    NW_RC(sg.put(ws->w_sig.p, sig, nsigs * 64, "H2D sig"));
-    NW_RC(sg.put(ws->w_signer.p, signer, nsigs * 4, "H2D signer"));
-    NW_RC(sg.put(ws->w_cert_first.p, first, nb * 4, "H2D first"));
-    NW_RC(sg.put(ws->w_cert_n.p, nv, nb * 4, "H2D n"));
-    cc.first = ws->w_cert_first.as<uint32_t>();
-    cc.nv = ws->w_cert_n.as<uint32_t>();
-    cc.sig = ws->w_sig.as<uint8_t>();
-    cc.signer = ws->w_signer.as<uint32_t>();
-    cc.msg_base = ws->w_msg.as<uint8_t>();
-    cc.msg_off = ws->w_msg_off.as<uint64_t>();
-    cc.msg_len = ws->w_msg_len.as<uint64_t>();
-    cc.cert_ok = ws->w_cert_ok.as<uint8_t>();
-    cc.sig_ok = want_sig_ok ? ws->w_ok.as<uint8_t>() : nullptr;   // verdict bytes from k_cert_finalize
-    return enqueue_certs(ctx, ws, cc, st);
+    NW_RC(sg.reserve(l.in.end, l.out.end, cs.bytes()));
+    NW_RC(upload_messages(sg, l.msgs, l.ml, msg, len, nsigs, total));
+    NW_RC(sg.put(l.sig, sig, nsigs * 64, "H2D sig"));
+    NW_RC(sg.put(l.signer, signer, nsigs * 4, "H2D signer"));
+    NW_RC(sg.put(l.first, first, nb * 4, "H2D first"));
+    NW_RC(sg.put(l.nv, nv, nb * 4, "H2D n"));
+    uint8_t* d = sg.dev(0);
+    cc.first = reinterpret_cast<const uint32_t*>(d + l.first);
+    cc.nv = reinterpret_cast<const uint32_t*>(d + l.nv);
+    cc.sig = d + l.sig;
+    cc.signer = reinterpret_cast<const uint32_t*>(d + l.signer);
+    cc.msg_base = d + l.msgs + l.ml.packed;
+    cc.msg_off = reinterpret_cast<const uint64_t*>(d + l.msgs + l.ml.off);
+    cc.msg_len = reinterpret_cast<const uint64_t*>(d + l.msgs + l.ml.len);
+    cc.cert_ok = d + l.in.end + l.cert_ok;
+    cc.sig_ok = want_sig_ok ? d + l.in.end + l.ok : nullptr;   // verdict bytes from k_cert_finalize
+    return enqueue_certs(ctx, ws, cc, cs, st);
 }
 
 // Shared body of strict_many / verify_batch: every signature in one "certificate" 0.  Cached keys
@@ -362,32 +304,35 @@ int run_generic(nw_ctx* ctx, const uint8_t* const* msg, const size_t* len, const
     cc.nsigs = n;
     cc.zseed = zseed;
     cc.cert_base = batch_index;
-    cc.batch_mode = batch_mode;
-    if (!cached) {
+    cc.batch_mode = batch_mode;   // cc.sig_ok / cc.cert_ok: where each path leaves its outputs
+    if (!cached && batch_mode) {
+        const uint32_t cnt = (uint32_t)n;
         MsmCall mc;
-        NW_RC(upload_sig_keys(ctx, ws, msg, len, pk, sig, n, st, batch_mode ? &mc.msg_flen : nullptr));
-        NW_TRY(ws->ensure(ws->w_ok, n + 16), "ws ok");
-        if (batch_mode) {
-            NW_TRY(ws->ensure(ws->w_cert_ok, 16), "ws verdict");
-            const uint32_t cnt = (uint32_t)n;
-            mc.nb = 1;
-            mc.counts = &cnt;
-            mc.nsig = n;
-            mc.zseed = zseed;
-            mc.batch_base = batch_index;
-            mc.batch_ok = ws->w_cert_ok.as<uint8_t>();
-            NW_RC(enqueue_msm(ctx, ws, mc, st));
-        } else {
-            NW_RC(enqueue_strict_var(ctx, ws, n, st, ws->w_ok.as<uint8_t>()));
-        }
+        mc.nb = 1;
+        mc.counts = &cnt;
+        mc.nsig = n;
+        mc.zseed = zseed;
+        mc.batch_base = batch_index;
+        NW_RC(run_msm(ctx, ws, st, mc, msg, len, pk, sig));
+        cc.cert_ok = mc.out;
+    } else if (!cached) {
+        const VarScratch vs(n);
+        const SigKeysLayout l(total, n);
+        Stager sg(ctx, ws, st);
+        NW_RC(sg.reserve(l.in.end, n + 16, vs.bytes()));
+        NW_RC(upload_messages(sg, l.msgs, l.ml, msg, len, n, total));
+        NW_RC(sg.put(l.sig, sig, n * 64, "H2D sig"));
+        NW_RC(sg.put(l.keys, pk, n * 32, "H2D keys"));
+        cc.sig_ok = sg.dev(l.in.end);
+        NW_RC(enqueue_strict_var(ctx, ws, n, sg.dev(0), l, vs, st, cc.sig_ok));
     } else if (small_call(n, total)) {
         // one-message paths (Signature::verify, one certificate's verify_batch): every input and the
         // preamble state in ONE staged H2D, no preamble kernels, both outputs in ONE D2H
         const PackedLayout l(total, n);
-        NW_TRY(ws->ensure(ws->w_io, l.in.end + l.out.end), "ws io");
-        NW_TRY(ws->h_io.ensure(std::max(l.in.end, l.out.end)), "pinned io");
+        const CertScratch cs = cert_scratch(ctx, 1, n, batch_mode, true, true);
+        NW_TRY(ws->reserve(l.in.end + l.out.end, cs.bytes(), std::max(l.in.end, l.out.end)), "workspace");
         uint8_t* h = ws->h_io.bytes();
-        uint8_t* d = ws->w_io.as<uint8_t>();
+        uint8_t* d = ws->io.bytes();
         uint8_t* d_out = d + l.in.end;
         uint64_t* hoff = reinterpret_cast<uint64_t*>(h + l.off);
         uint64_t* hlen = reinterpret_cast<uint64_t*>(h + l.len);
@@ -417,7 +362,7 @@ int run_generic(nw_ctx* ctx, const uint8_t* const* msg, const size_t* len, const
         cc.pre = &pre;
         cc.cert_ok = d_out + l.cert_ok;
         cc.sig_ok = ok_out ? d_out + l.ok : nullptr;
-        NW_RC(enqueue_certs(ctx, ws, cc, st));
+        NW_RC(enqueue_certs(ctx, ws, cc, cs, st));
         // the H2D above has completed in stream order before this copy overwrites the staging buffer
         NW_TRY(hipMemcpyAsync(h, d_out, l.out.end, hipMemcpyDeviceToHost, st), "D2H outputs");
         NW_RC(call.finish());
@@ -428,8 +373,8 @@ int run_generic(nw_ctx* ctx, const uint8_t* const* msg, const size_t* len, const
         const uint32_t first = 0, nv = (uint32_t)n;
         NW_RC(enqueue_staged(ctx, ws, st, cc, &first, &nv, msg, len, slots.data(), sig, ok_out != nullptr));
     }
-    if (ok_out) NW_TRY(hipMemcpyAsync(ok_out, ws->w_ok.p, n, hipMemcpyDeviceToHost, st), "D2H ok");
-    if (verdict_out) NW_TRY(hipMemcpyAsync(verdict_out, ws->w_cert_ok.p, 1, hipMemcpyDeviceToHost, st), "D2H");
+    if (ok_out) NW_TRY(hipMemcpyAsync(ok_out, cc.sig_ok, n, hipMemcpyDeviceToHost, st), "D2H ok");
+    if (verdict_out) NW_TRY(hipMemcpyAsync(verdict_out, cc.cert_ok, 1, hipMemcpyDeviceToHost, st), "D2H");
     return call.finish();
 }
 
@@ -463,27 +408,25 @@ int check_slots(nw_ctx* ctx, const uint32_t* signer_slot, size_t nsigs, const ch
 }
 
 // Digests of n messages on the workspace's stream st: the offsets and lengths go up through the
-// pinned block (layout l), stage_data(h_data, d_msg) sends the message bytes, and the digests come
-// back to the block at l.out.
+// pinned block (layout l) to the same offsets of the device block, stage_data(h_data, d_data) sends
+// the message bytes, and the digests come back to the block at l.out.
 template <class LenT, class StageData>
-int enqueue_digests(nw_ctx* ctx, Workspace* ws, hipStream_t st, size_t n, const DigestLayout& l, size_t data_bytes,
-                    const uint64_t* off, const LenT* len, const char* what_data, StageData&& stage_data) {
-    NW_TRY(ws->h_io.ensure(l.bytes()), "pinned io");
-    NW_TRY(ws->ensure(ws->w_msg, data_bytes + 16), "ws msg");
-    NW_TRY(ws->ensure(ws->w_msg_off, n * 8), "ws off");
-    NW_TRY(ws->ensure(ws->w_msg_len, n * 8), "ws len");
-    NW_TRY(ws->ensure(ws->w_out, n * 64), "ws out");
+int enqueue_digests(nw_ctx* ctx, Workspace* ws, hipStream_t st, size_t n, const DigestLayout& l, const uint64_t* off,
+                    const LenT* len, const char* what_data, StageData&& stage_data) {
+    // the call's one reservation, before the first upload (the kernel's last block may load past the data)
+    NW_TRY(ws->reserve(l.device_bytes() + 16, 0, l.bytes()), "workspace");
     uint8_t* h = ws->h_io.bytes();
+    uint8_t* d = ws->io.bytes();
     std::memcpy(h + l.off, off, n * 8);
     for (size_t i = 0; i < n; ++i) reinterpret_cast<uint64_t*>(h + l.len)[i] = len[i];
-    NW_TRY(hipMemcpyAsync(ws->w_msg_off.p, h + l.off, n * 8, hipMemcpyHostToDevice, st), "H2D off");
-    NW_TRY(hipMemcpyAsync(ws->w_msg_len.p, h + l.len, n * 8, hipMemcpyHostToDevice, st), "H2D len");
-    NW_TRY(stage_data(h + l.data, ws->w_msg.as<uint8_t>()), what_data);
-    NW_TRY(launch_sha512_many((uint32_t)n, ws->w_msg.as<uint8_t>(), ws->w_msg_off.as<uint64_t>(),
-                              ws->w_msg_len.as<uint64_t>(), ws->w_out.as<uint8_t>(), st),
+    NW_TRY(hipMemcpyAsync(d + l.off, h + l.off, n * 8, hipMemcpyHostToDevice, st), "H2D off");
+    NW_TRY(hipMemcpyAsync(d + l.len, h + l.len, n * 8, hipMemcpyHostToDevice, st), "H2D len");
+    NW_TRY(stage_data(h + l.data, d + l.data), what_data);
+    NW_TRY(launch_sha512_many((uint32_t)n, d + l.data, reinterpret_cast<const uint64_t*>(d + l.off),
+                              reinterpret_cast<const uint64_t*>(d + l.len), d + l.d_out, st),
            "k_sha512_many");
     // the uploads have completed in stream order before this copy may reuse the pinned block
-    NW_TRY(hipMemcpyAsync(h + l.out, ws->w_out.p, n * 64, hipMemcpyDeviceToHost, st), "D2H digests");
+    NW_TRY(hipMemcpyAsync(h + l.out, d + l.d_out, n * 64, hipMemcpyDeviceToHost, st), "D2H digests");
     return NW_OK;
 }
 
@@ -571,18 +514,14 @@ int nw_verify_batches_pk(nw_ctx* ctx, size_t nb, const uint32_t* counts, const u
     if (nb == 0) return NW_OK;
     HostCall call(ctx);
     NW_RC(call.begin());
-    Workspace* ws = call.ws;
     MsmCall mc;
-    NW_RC(upload_sig_keys(ctx, ws, msg, len, pk, sig, nsig, call.st, &mc.msg_flen));
-    NW_TRY(ws->ensure(ws->w_cert_ok, nb + 16), "ws verdicts");
     mc.nb = nb;
     mc.counts = counts;
     mc.nsig = nsig;
     mc.zseed = zseed;
     mc.batch_base = batch_base;
-    mc.batch_ok = ws->w_cert_ok.as<uint8_t>();
-    NW_RC(enqueue_msm(ctx, ws, mc, call.st));
-    NW_TRY(hipMemcpyAsync(batch_ok, ws->w_cert_ok.p, nb, hipMemcpyDeviceToHost, call.st), "D2H verdicts");
+    NW_RC(run_msm(ctx, call.ws, call.st, mc, msg, len, pk, sig));
+    NW_TRY(hipMemcpyAsync(batch_ok, mc.out, nb, hipMemcpyDeviceToHost, call.st), "D2H verdicts");
     return call.finish();
 }
 
@@ -594,24 +533,19 @@ int nw_verify_batch_partial(nw_ctx* ctx, const uint8_t* const* msg, const size_t
     if (n > 0x7FFFFFF0u) return NW_ERR_ARG;
     HostCall call(ctx);
     NW_RC(call.begin());
-    Workspace* ws = call.ws;
-    MsmCall mc;
-    NW_RC(upload_sig_keys(ctx, ws, msg, len, pk, sig, n, call.st, &mc.msg_flen));
-    NW_TRY(ws->ensure(ws->w_out, MSM_PT_WORDS * 4 + 16), "ws point");
     const uint32_t cnt = (uint32_t)n;
-    uint32_t* d_bad = nullptr;
+    MsmCall mc;
     mc.nb = 1;
     mc.counts = &cnt;
     mc.nsig = n;
     mc.zseed = zseed;
     mc.batch_base = batch_index;
     mc.z_off = z_offset;
-    mc.point_out = ws->w_out.as<uint32_t>();
-    mc.bad_out = &d_bad;
-    NW_RC(enqueue_msm(ctx, ws, mc, call.st));
+    mc.partial = true;
+    NW_RC(run_msm(ctx, call.ws, call.st, mc, msg, len, pk, sig));
     uint32_t hbad = 0;
-    NW_TRY(hipMemcpyAsync(point, ws->w_out.p, NW_POINT_BYTES, hipMemcpyDeviceToHost, call.st), "D2H point");
-    NW_TRY(hipMemcpyAsync(&hbad, d_bad, 4, hipMemcpyDeviceToHost, call.st), "D2H bad");
+    NW_TRY(hipMemcpyAsync(point, mc.out, NW_POINT_BYTES, hipMemcpyDeviceToHost, call.st), "D2H point");
+    NW_TRY(hipMemcpyAsync(&hbad, mc.bad, 4, hipMemcpyDeviceToHost, call.st), "D2H bad");
     NW_RC(call.finish());
     *bad = hbad ? 1 : 0;
     return NW_OK;
@@ -623,10 +557,13 @@ int nw_points_sum_is_identity(nw_ctx* ctx, const uint8_t (*points)[NW_POINT_BYTE
     NW_RC(call.begin());
     Workspace* ws = call.ws;
     hipStream_t st = call.st;
-    NW_TRY(ws->ensure(ws->w_misc, k * NW_POINT_BYTES + 64), "ws points");
-    if (k) NW_TRY(hipMemcpyAsync(ws->w_misc.p, points, k * NW_POINT_BYTES, hipMemcpyHostToDevice, st), "H2D points");
-    uint8_t* d_out = ws->w_misc.as<uint8_t>() + k * NW_POINT_BYTES;
-    NW_TRY(launch_msm_points_identity((uint32_t)k, ws->w_misc.as<uint32_t>(), d_out, st), "k_points_identity");
+    const size_t o_out = align256(k * NW_POINT_BYTES);   // the points, then the result byte
+    NW_TRY(ws->reserve(o_out + 64, 0, 0), "workspace");
+    uint8_t* d_points = ws->io.bytes();
+    uint8_t* d_out = d_points + o_out;
+    if (k) NW_TRY(hipMemcpyAsync(d_points, points, k * NW_POINT_BYTES, hipMemcpyHostToDevice, st), "H2D points");
+    NW_TRY(launch_msm_points_identity((uint32_t)k, reinterpret_cast<const uint32_t*>(d_points), d_out, st),
+           "k_points_identity");
     uint8_t r = 0;
     NW_TRY(hipMemcpyAsync(&r, d_out, 1, hipMemcpyDeviceToHost, st), "D2H");
     NW_RC(call.finish());
@@ -658,10 +595,10 @@ int nw_verify_certs(nw_ctx* ctx, const nw_cert* certs, size_t ncerts, const uint
     // also carry the preamble state (no preamble kernels) and go up in one H2D.  The signature array
     // of a large call goes up in 4 MiB chunks, each DMA overlapping the staging memcpy of the next.
     const CertsLayout l(nsigs, ncerts);
-    NW_TRY(ws->ensure(ws->w_io, l.in.end + l.out.end), "ws io");
-    NW_TRY(ws->h_io.ensure(std::max(l.in.end, l.out.end)), "pinned io");
+    const CertScratch cs = cert_scratch(ctx, ncerts, nsigs, 1, l.staged, true);
+    NW_TRY(ws->reserve(l.in.end + l.out.end, cs.bytes(), std::max(l.in.end, l.out.end)), "workspace");
     uint8_t* h = ws->h_io.bytes();
-    uint8_t* d_in = ws->w_io.as<uint8_t>();
+    uint8_t* d_in = ws->io.bytes();
     uint8_t* d_out = d_in + l.in.end;
     if (nsigs) std::memcpy(h + l.signer, signer_slot, nsigs * 4);
     std::memcpy(h + l.first, first.data(), ncerts * 4);
@@ -693,7 +630,7 @@ int nw_verify_certs(nw_ctx* ctx, const nw_cert* certs, size_t ncerts, const uint
     cc.cert_ok = d_out + l.cert_ok;
     cc.stake = reinterpret_cast<uint64_t*>(d_out + l.stake);
     cc.sig_ok = sig_ok && nsigs ? d_out + l.ok : nullptr;
-    NW_RC(enqueue_certs(ctx, ws, cc, st));   // on failure the lease synchronizes the stream (the H2D may be in flight)
+    NW_RC(enqueue_certs(ctx, ws, cc, cs, st));   // on failure the lease synchronizes the stream (the H2D may be in flight)
     // the H2D above has completed in stream order before this copy overwrites the staging buffer
     NW_TRY(hipMemcpyAsync(h, d_out, l.out.end, hipMemcpyDeviceToHost, st), "D2H outputs");
     NW_RC(call.finish());
@@ -725,8 +662,8 @@ int nw_verify_batches(nw_ctx* ctx, size_t nb, const uint32_t* first, const uint3
     cc.cert_base = batch_base;
     cc.batch_mode = 1;
     NW_RC(enqueue_staged(ctx, ws, st, cc, first, nvotes, msg, len, signer_slot, sig, sig_ok && nsigs));
-    if (sig_ok && nsigs) NW_TRY(hipMemcpyAsync(sig_ok, ws->w_ok.p, nsigs, hipMemcpyDeviceToHost, st), "D2H sig_ok");
-    if (batch_ok && nb) NW_TRY(hipMemcpyAsync(batch_ok, ws->w_cert_ok.p, nb, hipMemcpyDeviceToHost, st), "D2H");
+    if (sig_ok && nsigs) NW_TRY(hipMemcpyAsync(sig_ok, cc.sig_ok, nsigs, hipMemcpyDeviceToHost, st), "D2H sig_ok");
+    if (batch_ok && nb) NW_TRY(hipMemcpyAsync(batch_ok, cc.cert_ok, nb, hipMemcpyDeviceToHost, st), "D2H");
     return call.finish();
 }
 
@@ -769,7 +706,11 @@ int nw_verify_certs_dev(nw_ctx* ctx, size_t ncerts, const uint32_t* d_cert_first
     cc.flags = d_sig_flags;
     cc.stake = d_accepted_stake;
     cc.status = d_status;
-    int rc = enqueue_certs(ctx, lease.ws(), cc, st);
+    // a block that a pending call on this stream still reads is only freed after it (Workspace::ensure)
+    Workspace* ws = lease.ws();
+    const CertScratch cs = cert_scratch(ctx, ncerts, nsigs, 1, false, !d_sig_flags);
+    NW_TRY(ws->reserve(0, cs.bytes(), cc.sync_check ? 16 : 0), "workspace");
+    int rc = enqueue_certs(ctx, ws, cc, cs, st);
     if (rc == NW_ERR_ARG) {
         lease.synced();
         return rc;
@@ -809,7 +750,7 @@ int nw_sha512_many(nw_ctx* ctx, const uint8_t* base, const uint64_t* off, const 
     hipStream_t st = call.st;
     // everything through the pinned buffer (see Stager): offsets, lengths, then the data
     const DigestLayout l(n, span, false);
-    NW_RC(enqueue_digests(ctx, call.ws, st, n, l, span, roff.data(), len, "H2D data",
+    NW_RC(enqueue_digests(ctx, call.ws, st, n, l, roff.data(), len, "H2D data",
                           [&](uint8_t* h_data, uint8_t* d_msg) { return staged_h2d(h_data, d_msg, base + lo, span, st); }));
     NW_RC(call.finish());
     std::memcpy(out, call.ws->h_io.bytes() + l.out, n * 64);
@@ -857,8 +798,7 @@ int nw_sha512_many_async(nw_ctx* ctx, const uint8_t* const* msg, const size_t* l
     Workspace* ws = j->lease->ws();
     hipStream_t st = ws->stream;
     j->o_out = l.out;
-    NW_RC(enqueue_digests(ctx, ws, st, n, l, pack.total, pack.off.data(), len, "H2D messages", [&](uint8_t* h_data,
-                                                                                                  uint8_t* d_msg) {
+    NW_RC(enqueue_digests(ctx, ws, st, n, l, pack.off.data(), len, "H2D messages", [&](uint8_t* h_data, uint8_t* d_msg) {
         if (!pack.chunks()) return hipSuccess;
         return stage_chunks(pack.chunks(), pack.cb.data(),
                             [&](size_t c) {
@@ -917,11 +857,12 @@ int nw_sign_many(nw_ctx* ctx, const uint8_t (*seed)[32], const uint8_t* msgs, si
     NW_RC(call.begin());
     Workspace* ws = call.ws;
     hipStream_t st = call.st;
-    NW_TRY(ws->ensure(ws->w_misc, n * 32 + n * msg_len + 16), "ws misc");
-    NW_TRY(ws->ensure(ws->w_out, n * 96 + 16), "ws out");
-    uint8_t* d_seed = ws->w_misc.as<uint8_t>();
+    Bump b;
+    const size_t o_in = b.take(n * 32 + n * msg_len + 16), o_out = b.take(n * 96 + 16);
+    NW_TRY(ws->reserve(b.end, 0, 0), "workspace");
+    uint8_t* d_seed = ws->io.bytes() + o_in;
     uint8_t* d_msg = d_seed + n * 32;
-    uint8_t* d_pk = ws->w_out.as<uint8_t>();
+    uint8_t* d_pk = ws->io.bytes() + o_out;
     uint8_t* d_sig = d_pk + n * 32;
     NW_TRY(hipMemcpyAsync(d_seed, seed, n * 32, hipMemcpyHostToDevice, st), "H2D seed");
     NW_TRY(hipMemcpyAsync(d_msg, msgs, n * msg_len, hipMemcpyHostToDevice, st), "H2D msg");

@@ -50,14 +50,12 @@ int nw_core_batch_verify(nw_ctx* ctx, const nw_core_batch* b, const uint8_t zsee
     Workspace* ws = call.ws;
     hipStream_t st = call.st;
     const CoreLayout l(n, D, b->pre.size(), H, S, C, V);
-    NW_TRY(ws->ensure(ws->w_io, l.device_bytes()), "ws io");
-    NW_TRY(ws->h_io.ensure(l.pinned_bytes()), "pinned io");
-    // every scratch buffer at the size of the larger pass, before the first launch
-    if (S) NW_RC(reserve_certs(ctx, ws, 1, S, 0, l.s_staged, true));
-    if (C) NW_RC(reserve_certs(ctx, ws, C, V, 1, l.c_staged, true));
+    // the two signature passes lay their scratch over one block, sized for the larger
+    const CoreScratch cs(l, S, C, V, ctx->nkeys);
+    NW_TRY(ws->reserve(l.device_bytes(), cs.bytes(), l.pinned_bytes()), "workspace");
     // one staging pass over the struct of arrays
     uint8_t* h = ws->h_io.bytes();
-    uint8_t* d_in = ws->w_io.as<uint8_t>();
+    uint8_t* d_in = ws->io.bytes();
     uint8_t* d_work = d_in + l.work_at();
     uint8_t* d_out = d_in + l.out_at();
     auto put = [&](size_t at, const void* src, size_t bytes) {
@@ -125,7 +123,7 @@ int nw_core_batch_verify(nw_ctx* ctx, const nw_core_batch* b, const uint8_t zsee
         cc.batch_mode = 0;
         cc.pre = l.s_staged ? &spre : nullptr;
         cc.sig_ok = d_work + l.sok;
-        NW_RC(enqueue_certs(ctx, ws, cc, st));
+        NW_RC(enqueue_certs(ctx, ws, cc, cs.strict, st));
     }
     // 5. certificate pass: certificate j draws its coefficients at batch index cert_base + j
     if (C) {
@@ -142,7 +140,7 @@ int nw_core_batch_verify(nw_ctx* ctx, const nw_core_batch* b, const uint8_t zsee
         cc.batch_mode = 1;
         cc.pre = l.c_staged ? &cpre : nullptr;
         cc.cert_ok = d_work + l.cok;
-        NW_RC(enqueue_certs(ctx, ws, cc, st));
+        NW_RC(enqueue_certs(ctx, ws, cc, cs.certs, st));
     }
     // 6. verdicts
     CoreVerdictParams vp{};

@@ -11,12 +11,19 @@
 //   * the key cache (committee tables, basepoint comb) is shared state behind a reader/writer lock:
 //     every verify call holds it shared while it enqueues; nw_committee_load holds it exclusive and
 //     first waits for every in-flight call that may still read the tables;
-//   * every call leases a Workspace from a pool: its own stream, scratch buffers, pinned staging
-//     buffer and a completion event.  Host-buffer calls run on the workspace's stream and
-//     synchronize it; ``_dev`` calls run on the caller's stream and leave the workspace "pending"
-//     until its event completes — the next lease of that workspace waits on the event (stream
-//     order, or a host wait before any buffer is reallocated), so scratch is never reused while a
-//     kernel may still read it.
+//   * every call leases a Workspace from a pool: its own stream, two device blocks, pinned staging
+//     and a completion event.  Host-buffer calls run on the workspace's stream and synchronize it;
+//     ``_dev`` calls run on the caller's stream and leave the workspace "pending" until its event
+//     completes — the next lease of that workspace waits on the event (stream order, or a host wait
+//     before a block is reallocated), so device memory is never reused while a kernel may still read it.
+//
+// A workspace owns two device blocks, and every call lays both out afresh (nw_host_plan.h):
+//   io       inputs at the SAME offsets as in the pinned block h_io they are staged in, outputs behind them;
+//   scratch  what the kernels of one pipeline run pass among themselves (CertScratch / VarScratch /
+//            MsmScratch).  No segment carries state from one run to the next, so pipelines share it.
+// One reservation per call: a call computes its layouts first and grows memory in one place
+// (Workspace::reserve) before its first copy or launch: growing is hipFree + hipMalloc, and hipFree
+// waits for the whole device.  Nothing after that allocates.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -121,18 +128,15 @@ struct Key32Hash {
     }
 };
 
-// Per-call scratch: one per concurrently executing call.  Destroyed (nw_ctx_destroy) with its
+// Per-call memory: one per concurrently executing call.  Destroyed (nw_ctx_destroy) with its
 // stream idle and the device set.
 struct Workspace {
     hipStream_t stream = nullptr;   // stream of host-buffer calls
     hipEvent_t done = nullptr;      // recorded after the last enqueue that used these buffers
     hipStream_t last = nullptr;     // stream that event was recorded on
     bool pending = false;
-    DevBuf w_sig, w_signer, w_keys, w_sig_cert, w_cert_first, w_cert_n, w_msg, w_msg_off, w_msg_len, w_flags,
-        w_slow_count, w_slow_list, w_slow_slot, w_slow_buf, w_cert_ok, w_ok, w_misc, w_out, w_pbuf, w_pre, w_counts,
-        w_cursor, w_perm, w_io, w_var, w_status, w_msm_ent, w_msm_dig, w_msm_zs, w_msm_meta, w_msm_bkt, w_msm_part,
-        w_msm_wpart, w_pslow, w_cert_state, w_exact, w_pinfo;
-    HostBuf h_io, h_meta;
+    DevBuf io, scratch;     // the two device blocks (header comment)
+    HostBuf h_io, h_meta;   // pinned staging: the call's inputs / outputs, and the MSM metadata block
 
     ~Workspace() {
         if (done) (void)hipEventDestroy(done);
@@ -147,6 +151,8 @@ struct Workspace {
         }
         return b.ensure(bytes);
     }
+    // The one place a call grows memory, before its first copy or launch (sizes from its layouts).
+    hipError_t reserve(size_t io_bytes, size_t scratch_bytes, size_t pinned_bytes, size_t meta_bytes = 0);
 };
 
 constexpr size_t kMaxWorkspaces = 64;   // one per concurrently calling thread (the worker's 64)
@@ -294,13 +300,14 @@ struct CertCall {
     uint32_t *flags = nullptr, *status = nullptr;   // flags null: workspace scratch
     uint64_t* stake = nullptr;
 };
-// Enqueue the certificate pipeline on st (shared key lock held, workspace bound to st).
-int enqueue_certs(nw_ctx* ctx, Workspace* ws, const CertCall& c, hipStream_t st);
-// Grow the workspace scratch that a run over (ncerts, nsigs) takes (enqueue_certs does this for
-// itself).  A call that enqueues several runs on one stream reserves for all of them before its
-// first launch, so no buffer is reallocated under a kernel still in flight.
-int reserve_certs(nw_ctx* ctx, Workspace* ws, size_t ncerts, size_t nsigs, uint32_t batch_mode, bool prestaged,
-                  bool own_flags);
+// Scratch layout of a run against this context's key cache (shared key lock held); prestaged: CertCall::pre set.
+inline CertScratch cert_scratch(const nw_ctx* ctx, size_t ncerts, size_t nsigs, uint32_t batch_mode, bool prestaged,
+                                bool own_flags) {
+    return CertScratch(ncerts, nsigs, batch_mode, groups_signers(ctx->nkeys, prestaged, nsigs), ctx->nkeys, own_flags);
+}
+// Enqueue the certificate pipeline on st (shared key lock held, workspace bound to st) over the
+// scratch layout s, which the caller has reserved; allocates nothing.
+int enqueue_certs(nw_ctx* ctx, Workspace* ws, const CertCall& c, const CertScratch& s, hipStream_t st);
 
 // Wait for every call that may still read the key tables (exclusive key lock held).
 int drain_all(nw_ctx* ctx);
@@ -310,29 +317,25 @@ int drain_all(nw_ctx* ctx);
 bool lookup_slots(nw_ctx* ctx, const uint8_t (*pk)[32], size_t n, uint32_t* slots);
 
 // Host-buffer inputs of one call: segments are packed into the workspace's pinned buffer (256-B
-// aligned) and copied to their device buffers with asynchronous DMAs, so a call issues no
-// pageable copies and no intermediate synchronization (the call's final stream sync releases the
-// buffer).  Every segment is staged, large ones included: the runtime's pageable H2D runs at the
-// pinned rate only for host pages it has already seen; the first copy from a fresh buffer pins its
-// pages and took 7-10 ms per 8 MB on MI355X (profiles/r04/host_fed_trace_r04h.txt), and a node's
-// input buffers are fresh on every call (network receives).  The staging memcpy costs ~0.3 ms per
-// 8 MB at 31-34 GB/s (tools/host_fed_probe.py).
-// A call reserves the bytes it will stage before its first segment; a segment past that capacity
-// fails the call (NW_ERR_DEVICE, "staging overflow") instead of writing past the pinned buffer.
+// aligned) and copied to the same offsets of the device block with asynchronous DMAs, so a call
+// issues no pageable copies and no intermediate synchronization (the call's final stream sync
+// releases the buffer).  Every segment is staged, large ones included: a node's input buffers are
+// fresh on every call, and the first pageable copy from fresh pages is slow.
+// ``reserve`` is the call's one reservation (Workspace::reserve): the staged inputs, the outputs
+// behind them, scratch, MSM metadata.  Offsets come from the layout that sized the block (StagedLayout).
 class Stager {
 public:
     Stager(nw_ctx* ctx, Workspace* ws, hipStream_t st) : ctx_(ctx), ws_(ws), st_(st) {}
-    int reserve(size_t bytes);
-    static size_t room(size_t bytes) { return align256(bytes); }
-    uint8_t* alloc(size_t n);   // null (error text set) past the reservation
-    int copy(void* dst, const uint8_t* h, size_t n, const char* what);
-    int put(void* dst, const void* src, size_t n, const char* what);
+    int reserve(size_t in_bytes, size_t out_bytes, size_t scratch_bytes, size_t meta_bytes = 0);
+    uint8_t* host(size_t off) const { return ws_->h_io.bytes() + off; }
+    uint8_t* dev(size_t off) const { return ws_->io.bytes() + off; }   // the mirror of host(off)
+    int copy(size_t off, size_t n, const char* what);                  // one H2D of staged bytes to their mirror
+    int put(size_t off, const void* src, size_t n, const char* what);  // stage n bytes of src at off and upload them
 
 private:
     nw_ctx* ctx_;
     Workspace* ws_;
     hipStream_t st_;
-    size_t off_ = 0, cap_ = 0;
 };
 
 // Chunk c covers staging bytes [cb[c], cb[c+1]); copy_chunk(c) fills it; the DMAs go out in chunk
@@ -342,14 +345,10 @@ hipError_t stage_chunks(size_t nch, const size_t* cb, const std::function<void(s
 // Upload n bytes of host memory through pinned staging at h in kStageChunk chunks.
 hipError_t staged_h2d(uint8_t* h, uint8_t* dst, const uint8_t* src, size_t n, hipStream_t st);
 size_t message_bytes(const size_t* len, size_t n);
-// Pack per-signature messages into the workspace (MSGMODE 1).  fixed_len (MSM callers, whose kernel
-// reads either form): messages of one length laid out back to back go up as one block with no
-// offset / length arrays (*fixed_len = the length; UINT64_MAX otherwise).
-int upload_messages(nw_ctx* ctx, Workspace* ws, Stager& sg, const uint8_t* const* msg, const size_t* len, size_t n,
-                    size_t total, uint64_t* fixed_len = nullptr);
-// Upload per-signature messages, signatures and raw keys to the workspace (uncached-key paths).
-int upload_sig_keys(nw_ctx* ctx, Workspace* ws, const uint8_t* const* msg, const size_t* len,
-                    const uint8_t (*pk)[32], const uint8_t (*sig)[64], size_t n, hipStream_t st,
-                    uint64_t* fixed_len = nullptr);
+// Stage and upload per-signature messages (MSGMODE 1) into the MessageLayout ml at offset ``at``.
+// fixed_len (MSM callers, whose kernel reads either form): messages of one length laid out back to
+// back go up as one block with no offset / length arrays (*fixed_len = the length; UINT64_MAX otherwise).
+int upload_messages(Stager& sg, size_t at, const MessageLayout& ml, const uint8_t* const* msg, const size_t* len,
+                    size_t n, size_t total, uint64_t* fixed_len = nullptr);
 
 }  // namespace nw

@@ -145,6 +145,63 @@ struct CoreLayout {
     size_t pinned_bytes() const { return std::max(in.end, out.end); }
 };
 
+// Signer grouping on (1, release) or off (0: variant builds for the A/B of the grouping itself).
+#ifndef NW_GROUP_SIGNERS
+#define NW_GROUP_SIGNERS 1
+#endif
+// Group signatures by signer (key-table locality) above this batch size, and only when keys repeat
+// (at least kGroupMinSigsPerKey signatures per cached key on average): the worker's load (62,500
+// signatures over 100,000 keys, each key at most once) gains nothing from the order and would pay
+// the 100,000-slot scan (0.16 ms of a 0.47 ms batch, profiles/r02/kernel_stats_w_r02.csv).
+constexpr size_t kGroupMinSigs = 16384;
+constexpr size_t kGroupMinSigsPerKey = 4;
+static_assert(kStagedMaxSigs <= kGroupMinSigs, "staged calls never group");
+// signer grouping (device counting sort) when keys repeat
+inline bool groups_signers(size_t nkeys, bool prestaged, size_t nsigs) {
+    return NW_GROUP_SIGNERS && !prestaged && nsigs >= kGroupMinSigs && nkeys > 1 && nsigs >= kGroupMinSigsPerKey * nkeys;
+}
+
+// Device scratch of one run of the certificate pipeline (enqueue_certs).  Segments a run does not
+// use have size 0: the exact-path state without batch_mode, the grouping tables without ``group``,
+// the flags when the caller supplies its own.  The run writes every word before it reads it.
+struct CertScratch {
+    bool group;
+    Bump b;
+    size_t flags, sig_cert, slow_count, slow_list, slow_slot, pbuf, pre, status;
+    size_t slow_buf, pslow, cert_state, exact;   // batch_mode
+    size_t counts, cursor, perm, pinfo;          // group
+    CertScratch(size_t ncerts, size_t nsigs, uint32_t batch_mode, bool group, size_t nkeys, bool own_flags)
+        : group(group), flags(b.take(own_flags ? nsigs * 4 + 4 : 0)), sig_cert(b.take(nsigs * 4 + 4)),
+          slow_count(b.take(16)), slow_list(b.take(nsigs * 4 + 4)), slow_slot(b.take(nsigs * 4 + 4)),
+          pbuf(b.take(nsigs * (size_t)PBUF_WORDS * 4 + 16)), pre(b.take(nsigs * 40 + 16)), status(b.take(16)),
+          slow_buf(b.take(batch_mode ? nsigs * (size_t)SLOW_WORDS * 4 + 4 : 0)),
+          pslow(b.take(batch_mode ? nsigs * (size_t)160 + 16 : 0)), cert_state(b.take(batch_mode ? ncerts * 4 + 16 : 0)),
+          exact(b.take(batch_mode ? ncerts * 4 + 16 : 0)), counts(b.take(group ? nkeys * 4 + 16 : 0)),
+          cursor(b.take(group ? nkeys * 4 + 16 : 0)), perm(b.take(group ? nsigs * 4 + 16 : 0)),
+          pinfo(b.take(group ? nsigs * 8 + 16 : 0)) {}
+    size_t bytes() const { return b.end; }
+};
+
+// The two passes of a mixed Core batch lay their scratch over one block, sized for the larger: they
+// are serial in stream order and everything they keep lives in the CoreLayout block.
+struct CoreScratch {
+    CertScratch strict, certs;
+    CoreScratch(const CoreLayout& l, size_t S, size_t C, size_t V, size_t nkeys)
+        : strict(1, S, 0, groups_signers(nkeys, l.s_staged, S), nkeys, true),
+          certs(C, V, 1, groups_signers(nkeys, l.c_staged, V), nkeys, true) {}
+    size_t bytes() const { return std::max(strict.bytes(), certs.bytes()); }
+};
+
+// Device scratch of the strict variable-base verify (enqueue_strict_var): k_verify_var's table.
+struct VarScratch {
+    Bump b;
+    size_t flags, sig_cert, pbuf, pre, var;
+    explicit VarScratch(size_t n)
+        : flags(b.take(n * 4 + 4)), sig_cert(b.take(n * 4 + 4)), pbuf(b.take(n * (size_t)PBUF_WORDS * 4 + 16)),
+          pre(b.take(n * 40 + 16)), var(b.take(n * 320 * 4 + 16)) {}
+    size_t bytes() const { return b.end; }
+};
+
 // Staged block of per-signature messages (upload_messages): the packed bytes, offsets, lengths.
 struct MessageLayout {
     Bump b;
@@ -152,17 +209,36 @@ struct MessageLayout {
     MessageLayout(size_t total, size_t n) : packed(b.take(total + 8)), off(b.take(n * 8 + 8)), len(b.take(n * 8 + 8)) {}
     size_t bytes() const { return b.end; }
 };
+// Blocks of the segment-by-segment paths: the messages (ml, at msgs), then enqueue_staged's arrays
+// and outputs, or the signatures and raw keys of a call on keys outside the cache.
+struct StagedLayout {
+    MessageLayout ml;
+    Bump in, out;
+    size_t msgs, sig, signer, first, nv, cert_ok, ok;
+    StagedLayout(size_t total, size_t nsigs, size_t nb)
+        : ml(total, nsigs), msgs(in.take(ml.bytes())), sig(in.take(nsigs * 64)), signer(in.take(nsigs * 4)),
+          first(in.take(nb * 4)), nv(in.take(nb * 4)), cert_ok(out.take(nb + 16)), ok(out.take(nsigs + 16)) {}
+};
+struct SigKeysLayout {
+    MessageLayout ml;
+    Bump in;
+    size_t msgs, sig, keys;
+    SigKeysLayout(size_t total, size_t n)
+        : ml(total, n), msgs(in.take(ml.bytes())), sig(in.take(n * 64)), keys(in.take(n * 32)) {}
+};
 
 // Pinned block of a digest call: offsets, lengths and the message bytes go up; the n digests come
 // back either behind the data (asynchronous jobs: the block lives until nw_job_wait) or over the
-// start of the block once the uploads are done (out_behind false).
+// start of the block once the uploads are done (out_behind false).  In the device mirror the digests
+// are always behind the data (d_out): the kernel still reads the offsets while it writes them.
 struct DigestLayout {
     Bump b;
-    size_t off, len, data, out, out_end;
+    size_t off, len, data, out, out_end, d_out, d_end;
     DigestLayout(size_t n, size_t data_bytes, bool out_behind)
         : off(b.take(n * 8)), len(b.take(n * 8)), data(b.take(data_bytes)), out(out_behind ? b.take(n * 64) : 0),
-          out_end(align256(out + n * 64)) {}
+          out_end(align256(out + n * 64)), d_out(out_behind ? out : b.end), d_end(align256(d_out + n * 64)) {}
     size_t bytes() const { return std::max(b.end, out_end); }
+    size_t device_bytes() const { return d_end; }
 };
 
 // Asynchronous digest: the messages packed at 16-byte aligned offsets, cut into chunks of whole
@@ -240,6 +316,20 @@ struct MsmMetaLayout {
         : bfirst(b.take(nb * 4)), bcount(b.take(nb * 4)), sig_batch(b.take(nsig * 4 + 4)),
           wfirst(b.take(p.wfirst.size() * 4)), tasks(b.take(p.tasks.size() * sizeof(MsmTask) + 16)),
           bad(b.take(nb * 4)) {}
+    size_t bytes() const { return b.end; }
+};
+
+// Scratch of one MSM run: the metadata block (uploaded) and what the kernels pass among themselves.
+struct MsmScratch {
+    MsmMetaLayout ml;
+    Bump b;
+    size_t meta, ent, dig, zs, bkt, part, wpart;
+    MsmScratch(size_t nb, size_t nsig, const MsmPlan& p)
+        : ml(nb, nsig, p), meta(b.take(ml.bytes())), ent(b.take(2 * nsig * MSM_ENT_WORDS * 4 + 16)),
+          dig(b.take((size_t)p.NA * 2 * nsig * 2 + 16)), zs(b.take((size_t)MSM_ZS_WORDS * nsig * 4 + 16)),
+          bkt(b.take(p.tasks.size() * ((size_t)1 << (p.C - 1)) * MSM_PT_WORDS * 4 + 16)),
+          part(b.take(p.tasks.size() * 128 * MSM_PT_WORDS * 4 + 16)),
+          wpart(b.take((p.tasks.size() + nb * p.NA) * MSM_PT_WORDS * 4 + 16)) {}
     size_t bytes() const { return b.end; }
 };
 

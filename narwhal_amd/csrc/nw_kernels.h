@@ -101,7 +101,7 @@ struct FinalizeParams {
     const uint32_t* cert_state;    // [ncerts] CS_*
     uint8_t* cert_ok;              // [ncerts] (may be null)
     uint64_t* accepted_stake;      // [ncerts] (may be null)
-    uint8_t* sig_ok;               // [nsigs] strict verdict bytes (may be null; k_flags_to_ok fused)
+    uint8_t* sig_ok;               // [nsigs] strict verdict bytes (may be null; written by k_cert_finalize)
     uint32_t* exact_count;         // device counter (zeroed by the preamble) of ...
     uint32_t* exact_list;          // [ncerts] ... certificates whose verdict needs the exact sum (k_cert_exact)
 };
@@ -132,7 +132,6 @@ hipError_t launch_prep_expand(uint32_t ncerts, uint32_t nsigs, uint32_t nkeys, c
 hipError_t launch_group_scatter(uint32_t n, uint32_t nkeys, const uint32_t* signer, const uint32_t* sig_cert,
                                 const uint32_t* counts, uint32_t* cursor, uint32_t* perm, uint2* pinfo,
                                 hipStream_t st);
-hipError_t launch_flags_to_ok(uint32_t n, const uint32_t* flags, uint8_t* ok, hipStream_t st);
 // Tables for nk keys at tab + j * stride (u32 words); negtab: each followed by its negated copy
 // (stride >= 2 comb_words(window)).
 hipError_t launch_key_prep(uint32_t nk, const uint32_t* keys_raw, uint32_t* key_info, uint32_t* bases,

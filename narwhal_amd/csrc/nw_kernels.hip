@@ -341,11 +341,6 @@ __global__ void __launch_bounds__(256) k_expand_count(uint32_t ncerts, uint32_t 
     if (bad && status) atomicOr(status, (uint32_t)NW_ERR_ARG);
 }
 
-__global__ void __launch_bounds__(256) k_flags_to_ok(uint32_t n, const uint32_t* flags, uint8_t* ok) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) ok[i] = (flags[i] & NW_F_STRICT) ? 1 : 0;
-}
-
 // Exact path, step 2 (slow_mul in nw_verify_kernels.h) over up to 256 workgroups.
 __global__ void __launch_bounds__(256) k_slow_mul(VerifyParams a) {
     __shared__ uint32_t tab[SLOW_MUL_QUADS][8][40];
@@ -453,12 +448,6 @@ hipError_t launch_group_scatter(uint32_t n, uint32_t nkeys, const uint32_t* sign
     else
         hipLaunchKernelGGL(k_scatter_slots, dim3(blocks_for(n, 256)), dim3(256), 0, st, n, nkeys, signer, sig_cert,
                            cursor, perm, pinfo);
-    return hipGetLastError();
-}
-
-hipError_t launch_flags_to_ok(uint32_t n, const uint32_t* flags, uint8_t* ok, hipStream_t st) {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_flags_to_ok, dim3(blocks_for(n, 256)), dim3(256), 0, st, n, flags, ok);
     return hipGetLastError();
 }
 

@@ -7,26 +7,16 @@
 
 namespace nw {
 
-int Stager::reserve(size_t bytes) {
+int Stager::reserve(size_t in_bytes, size_t out_bytes, size_t scratch_bytes, size_t meta_bytes) {
     nw_ctx* ctx = ctx_;
-    NW_TRY(ws_->h_io.ensure(bytes + 16 * 256), "pinned io");
-    cap_ = bytes;
+    const size_t tail = 16 * 256;   // what a kernel's wide loads may touch past the last segment
+    NW_TRY(ws_->reserve(in_bytes + out_bytes + tail, scratch_bytes, in_bytes + tail, meta_bytes), "workspace");
     return NW_OK;
 }
 
-uint8_t* Stager::alloc(size_t n) {
-    if (n > cap_ || off_ > cap_ - n) {
-        set_error(ctx_, "staging overflow");
-        return nullptr;
-    }
-    uint8_t* h = ws_->h_io.bytes() + off_;
-    off_ = align256(off_ + n);
-    return h;
-}
-
-int Stager::copy(void* dst, const uint8_t* h, size_t n, const char* what) {
+int Stager::copy(size_t off, size_t n, const char* what) {
     nw_ctx* ctx = ctx_;
-    if (n) NW_TRY(hipMemcpyAsync(dst, h, n, hipMemcpyHostToDevice, st_), what);
+    if (n) NW_TRY(hipMemcpyAsync(dev(off), host(off), n, hipMemcpyHostToDevice, st_), what);
     return NW_OK;
 }
 
@@ -115,20 +105,17 @@ hipError_t staged_h2d(uint8_t* h, uint8_t* dst, const uint8_t* src, size_t n, hi
 // issued once its piece is staged, so the memcpy of one piece runs under the DMA of the previous.
 constexpr size_t kPutPiece = 1u << 20;
 
-int Stager::put(void* dst, const void* src, size_t n, const char* what) {
+int Stager::put(size_t off, const void* src, size_t n, const char* what) {
     nw_ctx* ctx = ctx_;
-    if (!n) return NW_OK;
-    uint8_t* h = alloc(n);
-    if (!h) return NW_ERR_DEVICE;
     if (n >= kStageParallelMin) {
-        NW_TRY(staged_h2d(h, static_cast<uint8_t*>(dst), static_cast<const uint8_t*>(src), n, st_), what);
+        NW_TRY(staged_h2d(host(off), dev(off), static_cast<const uint8_t*>(src), n, st_), what);
         return NW_OK;
     }
     const size_t piece = n >= 2 * kPutPiece ? kPutPiece : n;
     for (size_t o = 0; o < n; o += piece) {
         const size_t m = std::min(piece, n - o);
-        std::memcpy(h + o, static_cast<const uint8_t*>(src) + o, m);
-        NW_RC(copy(static_cast<uint8_t*>(dst) + o, h + o, m, what));
+        std::memcpy(host(off + o), static_cast<const uint8_t*>(src) + o, m);
+        NW_RC(copy(off + o, m, what));
     }
     return NW_OK;
 }
@@ -139,12 +126,9 @@ size_t message_bytes(const size_t* len, size_t n) {
     return total;
 }
 
-int upload_messages(nw_ctx* ctx, Workspace* ws, Stager& sg, const uint8_t* const* msg, const size_t* len, size_t n,
-                    size_t total, uint64_t* fixed_len) {
-    NW_TRY(ws->ensure(ws->w_msg, total + 8), "ws msg");
-    const MessageLayout ml(total, n);
-    uint8_t* h = sg.alloc(ml.bytes());
-    if (!h) return NW_ERR_DEVICE;
+int upload_messages(Stager& sg, size_t at, const MessageLayout& ml, const uint8_t* const* msg, const size_t* len,
+                    size_t n, size_t total, uint64_t* fixed_len) {
+    uint8_t* h = sg.host(at);
     uint8_t* packed = h + ml.packed;
     if (fixed_len) {
         // messages of one length laid out back to back (the worker's 8-byte messages, numpy rows)
@@ -154,11 +138,9 @@ int upload_messages(nw_ctx* ctx, Workspace* ws, Stager& sg, const uint8_t* const
         if (ok) {
             if (total) std::memcpy(packed, msg[0], total);
             std::memset(packed + total, 0, 8);
-            return sg.copy(ws->w_msg.p, packed, total + 8, "H2D msg");
+            return sg.copy(at + ml.packed, total + 8, "H2D msg");
         }
     }
-    NW_TRY(ws->ensure(ws->w_msg_off, n * 8 + 8), "ws msg_off");
-    NW_TRY(ws->ensure(ws->w_msg_len, n * 8 + 8), "ws msg_len");
     uint64_t* off = reinterpret_cast<uint64_t*>(h + ml.off);
     uint64_t* ln = reinterpret_cast<uint64_t*>(h + ml.len);
     // messages laid out back to back in the caller's memory (the worker's fixed 8-byte messages,
@@ -178,22 +160,9 @@ int upload_messages(nw_ctx* ctx, Workspace* ws, Stager& sg, const uint8_t* const
             if (len[i]) std::memcpy(packed + off[i], msg[i], len[i]);
     }
     std::memset(packed + pos, 0, 8);
-    NW_RC(sg.copy(ws->w_msg.p, packed, total + 8, "H2D msg"));
-    NW_RC(sg.copy(ws->w_msg_off.p, reinterpret_cast<uint8_t*>(off), n * 8, "H2D off"));
-    return sg.copy(ws->w_msg_len.p, reinterpret_cast<uint8_t*>(ln), n * 8, "H2D len");
-}
-
-int upload_sig_keys(nw_ctx* ctx, Workspace* ws, const uint8_t* const* msg, const size_t* len,
-                    const uint8_t (*pk)[32], const uint8_t (*sig)[64], size_t n, hipStream_t st,
-                    uint64_t* fixed_len) {
-    const size_t total = message_bytes(len, n);
-    Stager sg(ctx, ws, st);
-    NW_RC(sg.reserve(MessageLayout(total, n).bytes() + Stager::room(n * 64) + Stager::room(n * 32)));
-    NW_RC(upload_messages(ctx, ws, sg, msg, len, n, total, fixed_len));
-    NW_TRY(ws->ensure(ws->w_sig, n * 64 + 64), "ws sig");
-    NW_TRY(ws->ensure(ws->w_keys, n * 32 + 32), "ws keys");
-    NW_RC(sg.put(ws->w_sig.p, sig, n * 64, "H2D sig"));
-    return sg.put(ws->w_keys.p, pk, n * 32, "H2D keys");
+    NW_RC(sg.copy(at + ml.packed, total + 8, "H2D msg"));
+    NW_RC(sg.copy(at + ml.off, n * 8, "H2D off"));
+    return sg.copy(at + ml.len, n * 8, "H2D len");
 }
 
 }  // namespace nw

@@ -15,6 +15,14 @@ int fail(nw_ctx* c, hipError_t e, const char* what) {
     return e == hipErrorOutOfMemory ? NW_ERR_NOMEM : NW_ERR_DEVICE;
 }
 
+hipError_t Workspace::reserve(size_t io_bytes, size_t scratch_bytes, size_t pinned_bytes, size_t meta_bytes) {
+    hipError_t e = ensure(io, io_bytes);
+    if (e == hipSuccess) e = ensure(scratch, scratch_bytes);
+    if (e == hipSuccess) e = h_io.ensure(pinned_bytes);
+    if (e == hipSuccess) e = h_meta.ensure(meta_bytes);
+    return e;
+}
+
 Lease::Lease(nw_ctx* ctx, hipStream_t st, size_t pinned_hint) : ctx_(ctx) {
     std::unique_lock<std::mutex> g(ctx->pool_mu);
     for (;;) {

@@ -56,6 +56,56 @@ static void check_msm(const std::vector<uint32_t>& counts) {
     for (const MsmTask& t : p.tasks) CHECK(t.e0 < t.e1 && t.e1 - t.e0 <= (uint32_t)MSM_CH && t.e1 <= 2 * nsig);
 }
 
+// A scratch layout's segments, in layout order, tile [0, bytes) at 256-byte aligned offsets.
+static void check_tiling(const std::vector<size_t>& at, size_t bytes) {
+    size_t prev = 0;
+    for (size_t o : at) {
+        CHECK(o % 256 == 0 && o >= prev && o <= bytes);
+        prev = o;
+    }
+    CHECK(at.empty() || at[0] == 0);
+    CHECK(bytes % 256 == 0);
+}
+
+static void check_scratch(size_t nsigs, size_t ncerts) {
+    for (uint32_t batch_mode = 0; batch_mode < 2; ++batch_mode)
+        for (int group = 0; group < 2; ++group)
+            for (size_t nkeys : {(size_t)4, (size_t)100000})
+                for (int own = 0; own < 2; ++own) {
+                    const CertScratch s(ncerts, nsigs, batch_mode, group != 0, nkeys, own != 0);
+                    check_tiling({s.flags, s.sig_cert, s.slow_count, s.slow_list, s.slow_slot, s.pbuf, s.pre, s.status,
+                                  s.slow_buf, s.pslow, s.cert_state, s.exact, s.counts, s.cursor, s.perm, s.pinfo},
+                                 s.bytes());
+                    CHECK((s.pslow == s.slow_buf) == (batch_mode == 0));
+                    CHECK((s.bytes() == s.counts) == (group == 0));
+                    CHECK(s.sig_cert - s.flags >= (own ? nsigs * 4 + 4 : 0));
+                    CHECK(s.bytes() - s.pinfo >= (group ? nsigs * 8 + 16 : 0));
+                    if (nsigs <= 16385) {   // small enough to touch: the last byte each kernel may write
+                        std::vector<uint8_t> d(s.bytes());
+                        d[s.status + 15] = 1;
+                        d[s.pre + nsigs * 40 + 15] = 1;
+                        if (batch_mode) d[s.slow_buf + nsigs * (size_t)SLOW_WORDS * 4 + 3] = 1, d[s.exact + ncerts * 4 + 15] = 1;
+                        if (group) d[s.pinfo + nsigs * 8 + 15] = 1;
+                    }
+                }
+    const VarScratch v(nsigs);
+    check_tiling({v.flags, v.sig_cert, v.pbuf, v.pre, v.var}, v.bytes());
+    CHECK(v.bytes() - v.var >= nsigs * 320 * 4 + 16);
+}
+
+static void check_msm_scratch(const std::vector<uint32_t>& counts) {
+    size_t nsig = 0;
+    for (uint32_t c : counts) nsig += c;
+    const MsmPlan p = msm_plan(counts.data(), counts.size(), nsig);
+    const MsmScratch s(counts.size(), nsig, p);
+    check_tiling({s.meta, s.ent, s.dig, s.zs, s.bkt, s.part, s.wpart}, s.bytes());
+    CHECK(s.ent - s.meta == s.ml.bytes());
+    CHECK(s.bytes() - s.wpart >= (p.tasks.size() + counts.size() * p.NA) * MSM_PT_WORDS * 4 + 16);
+    std::vector<uint8_t> d(s.bytes());
+    d[s.meta + s.ml.bad + counts.size() * 4 - 1] = 1;
+    d[s.bkt + p.tasks.size() * ((size_t)1 << (p.C - 1)) * MSM_PT_WORDS * 4 + 15] = 1;
+}
+
 static void check_digest(const std::vector<size_t>& len) {
     const DigestPack p = digest_pack(len.data(), len.size());
     const DigestLayout l(len.size(), p.total, true);
@@ -89,6 +139,18 @@ int main() {
     }
     for (const auto& counts : std::vector<std::vector<uint32_t>>{{1}, {0, 5, 0}, {511}, {512}, {1024}, {1025}, {67, 1025, 3}})
         check_msm(counts);
+    for (const auto& sc : std::vector<std::pair<size_t, size_t>>{{0, 0}, {1, 1}, {256, 16}, {257, 17}, {4096, 1}, {4097, 1},
+                                                                 {16384, 128}, {16385, 129}, {0xFFFFFFF0u, 1}})
+        check_scratch(sc.first, sc.second);
+    for (const auto& counts : std::vector<std::vector<uint32_t>>{{3}, {511}, {512}, {3, 520}}) check_msm_scratch(counts);
+    {
+        const CoreLayout l(20400, 20400, 64 * 20400, 20000, 20000, 200, 20000);
+        const CoreScratch cs(l, 20000, 200, 20000, 4);
+        CHECK(cs.strict.group && cs.certs.group && cs.bytes() == std::max(cs.strict.bytes(), cs.certs.bytes()));
+        const CoreLayout l2(4, 4, 256, 3, 3, 1, 67);
+        const CoreScratch cs2(l2, 3, 1, 67, 4);
+        CHECK(!cs2.strict.group && !cs2.certs.group && cs2.bytes() == cs2.certs.bytes());
+    }
     const size_t M4 = (size_t)4 << 20;
     check_digest({});
     check_digest({0, 0});
@@ -99,6 +161,10 @@ int main() {
         const MessageLayout m(total, 3);
         CHECK(l.pre + l.pl.bytes() == l.in.end && m.len + 3 * 8 + 8 <= m.bytes());
         CHECK(small_call(3, total) == (l.in.end < kSmallCallBytes));
+        const StagedLayout s(total, 3, 2);
+        const SigKeysLayout k(total, 3);
+        CHECK(s.msgs + s.ml.bytes() == s.sig && s.nv + 2 * 4 <= s.in.end && s.ok + 3 + 16 <= s.out.end);
+        CHECK(k.msgs + k.ml.bytes() == k.sig && k.keys + 3 * 32 <= k.in.end);
     }
     auto words = [](int w) { return (size_t)((256 + w - 1) / w) * ((1u << (w - 1)) + 1) * 32; };
     CHECK(committee_window(10000, 1.25, (size_t)200 << 30, words) == 13);

@@ -51,9 +51,19 @@ void t_message_layout(size_t total, size_t n, size_t* o) {
     const MessageLayout l(total, n);
     o[0] = l.packed; o[1] = l.off; o[2] = l.len; o[3] = l.bytes();
 }
+void t_staged_layout(size_t total, size_t nsigs, size_t nb, size_t* o) {
+    const StagedLayout l(total, nsigs, nb);
+    const size_t at[] = {l.msgs, l.sig, l.signer, l.first, l.nv, l.in.end, l.cert_ok, l.ok, l.out.end, l.ml.bytes()};
+    std::memcpy(o, at, sizeof at);
+}
+void t_sig_keys_layout(size_t total, size_t n, size_t* o) {
+    const SigKeysLayout l(total, n);
+    const size_t at[] = {l.msgs, l.sig, l.keys, l.in.end, l.ml.bytes()};
+    std::memcpy(o, at, sizeof at);
+}
 void t_digest_layout(size_t n, size_t data, int behind, size_t* o) {
     const DigestLayout l(n, data, behind != 0);
-    o[0] = l.off; o[1] = l.len; o[2] = l.data; o[3] = l.out; o[4] = l.bytes();
+    o[0] = l.off; o[1] = l.len; o[2] = l.data; o[3] = l.out; o[4] = l.bytes(); o[5] = l.d_out; o[6] = l.device_bytes();
 }
 // head: C, NA, NR, one_task_windows, ntasks; meta: the metadata block's offsets then its size
 int t_msm_plan(const uint32_t* counts, size_t nb, size_t nsig, uint32_t* head, uint32_t* bfirst, uint32_t* bcount,
@@ -70,6 +80,31 @@ int t_msm_plan(const uint32_t* counts, size_t nb, size_t nsig, uint32_t* head, u
     meta[0] = l.bfirst; meta[1] = l.bcount; meta[2] = l.sig_batch; meta[3] = l.wfirst; meta[4] = l.tasks;
     meta[5] = l.bad; meta[6] = l.bytes();
     return 0;
+}
+int t_groups_signers(size_t nkeys, int prestaged, size_t nsigs) { return groups_signers(nkeys, prestaged != 0, nsigs); }
+void t_cert_scratch(size_t ncerts, size_t nsigs, uint32_t batch_mode, int group, size_t nkeys, int own_flags, size_t* o) {
+    const CertScratch s(ncerts, nsigs, batch_mode, group != 0, nkeys, own_flags != 0);
+    const size_t at[] = {s.flags, s.sig_cert, s.slow_count, s.slow_list, s.slow_slot, s.pbuf, s.pre, s.status,
+                         s.slow_buf, s.pslow, s.cert_state, s.exact, s.counts, s.cursor, s.perm, s.pinfo, s.bytes()};
+    std::memcpy(o, at, sizeof at);
+}
+void t_var_scratch(size_t n, size_t* o) {
+    const VarScratch s(n);
+    const size_t at[] = {s.flags, s.sig_cert, s.pbuf, s.pre, s.var, s.bytes()};
+    std::memcpy(o, at, sizeof at);
+}
+void t_msm_scratch(const uint32_t* counts, size_t nb, size_t nsig, size_t* o) {
+    const MsmPlan p = msm_plan(counts, nb, nsig);
+    const MsmScratch s(nb, nsig, p);
+    const size_t at[] = {s.meta, s.ent, s.dig, s.zs, s.bkt, s.part, s.wpart, s.bytes(), s.ml.bytes()};
+    std::memcpy(o, at, sizeof at);
+}
+// the Core pipeline's reservation, then the sizes of its two passes' layouts
+void t_core_scratch(size_t S, size_t C, size_t V, size_t nkeys, size_t* o) {
+    const CoreLayout l(S + C, S + C, 64 * (S + C), S, S, C, V);
+    const CoreScratch s(l, S, C, V, nkeys);
+    o[0] = s.bytes(); o[1] = s.strict.bytes(); o[2] = s.certs.bytes();
+    o[3] = l.s_staged; o[4] = l.c_staged;
 }
 long t_digest_pack(const size_t* len, size_t n, uint64_t* off, size_t* total, size_t* cb, size_t* cm, size_t cap) {
     const DigestPack p = digest_pack(len, n);
@@ -272,14 +307,101 @@ def test_message_layout(lib, total, n):
     check_block(list(o)[:3], [total + 8, n * 8 + 8, n * 8 + 8], o[3])
 
 
+@pytest.mark.parametrize("total,n,nb", [(0, 0, 0), (8, 1, 1), (5, 3, 2), (2 * MIB + 5, 3, 1), (500000, 62500, 64)])
+def test_segment_by_segment_layouts(lib, total, n, nb):
+    """The blocks of the staged paths: the message block, then each array where the call puts it; the
+    outputs no smaller than the separately allocated verdict buffers were (nb + 16, nsigs + 16)."""
+    msgs = align256(total + 8) + 2 * align256(n * 8 + 8)
+    o = _sizes(10)
+    lib.t_staged_layout(_sz(total), _sz(n), _sz(nb), o)
+    assert o[9] == msgs
+    check_block(list(o)[:5], [msgs, n * 64, n * 4, nb * 4, nb * 4], o[5])
+    check_block(list(o)[6:8], [nb + 16, n + 16], o[8])
+    o = _sizes(5)
+    lib.t_sig_keys_layout(_sz(total), _sz(n), o)
+    assert o[4] == msgs
+    check_block(list(o)[:3], [msgs, n * 64, n * 32], o[3])
+
+
 @pytest.mark.parametrize("n,data", [(1, 0), (1, 13), (5, 2 * MIB + 1), (1250, 1250 * 508064)])
 def test_digest_layouts(lib, n, data):
-    o = _sizes(5)
+    o = _sizes(7)
     lib.t_digest_layout(_sz(n), _sz(data), 1, o)        # asynchronous: the digests behind the data
     check_block(list(o)[:4], [n * 8, n * 8, data, n * 64], o[4])
+    assert o[5] == o[3] and o[6] == o[4]                # the device block mirrors the pinned one
     lib.t_digest_layout(_sz(n), _sz(data), 0, o)        # synchronous: the digests over the start of the block
     check_block(list(o)[:3], [n * 8, n * 8, data], align256(o[2] + data))
     assert o[3] == 0 and o[4] == max(align256(o[2] + data), align256(n * 64))
+    # ... of the pinned block only: on the device they stay behind the data the kernel is reading
+    check_block(list(o)[:3] + [o[5]], [n * 8, n * 8, data, n * 64], o[6])
+
+
+# ---------------------------------------------------------------- scratch layouts
+# The byte counts below restate what each pipeline asked of its separately allocated scratch buffers
+# before they became segments of one block, slack included.
+
+PBUF_WORDS, SLOW_WORDS = 21, 44
+SCRATCH_SHAPES = [(0, 0), (1, 1), (256, 16), (257, 17), (4096, 1), (4097, 1), (16384, 128), (16385, 129),
+                  (0xFFFFFFF0, 1)]                                   # the last: size_t arithmetic only
+
+
+def check_scratch(offsets, want, total):
+    """Segments in layout order: each at a 256-byte aligned offset, at least as large as ``want`` asks,
+    pairwise disjoint; a segment nobody asked for has size 0; the block is the sum of the segments."""
+    check_block(offsets, want, total)
+    ends = list(offsets[1:]) + [total]
+    assert list(offsets) == sorted(offsets)
+    for o, e, w in zip(offsets, ends, want):
+        assert e - o >= w
+        assert (e == o) == (w == 0)
+    assert total == sum(align256(w) for w in want)
+
+
+def _cert_scratch_bytes(ncerts, nsigs, batch_mode, group, nkeys, own_flags):
+    always = [nsigs * 4 + 4 if own_flags else 0, nsigs * 4 + 4, 16, nsigs * 4 + 4, nsigs * 4 + 4,
+              nsigs * PBUF_WORDS * 4 + 16, nsigs * 40 + 16, 16]      # flags sig_cert slow_count slow_list slow_slot pbuf pre status
+    batch = [nsigs * SLOW_WORDS * 4 + 4, nsigs * 160 + 16, ncerts * 4 + 16, ncerts * 4 + 16]   # slow_buf pslow cert_state exact
+    grp = [nkeys * 4 + 16, nkeys * 4 + 16, nsigs * 4 + 16, nsigs * 8 + 16]                     # counts cursor perm pinfo
+    return always + (batch if batch_mode else [0] * 4) + (grp if group else [0] * 4)
+
+
+@pytest.mark.parametrize("nsigs,ncerts", SCRATCH_SHAPES)
+def test_cert_scratch(lib, nsigs, ncerts):
+    for batch_mode in (0, 1):
+        for group, nkeys in ((0, 4), (0, 100000), (1, 4), (1, 100000)):
+            for own_flags in (1, 0):
+                o = _sizes(17)
+                lib.t_cert_scratch(_sz(ncerts), _sz(nsigs), batch_mode, group, _sz(nkeys), own_flags, o)
+                want = _cert_scratch_bytes(ncerts, nsigs, batch_mode, group, nkeys, own_flags)
+                check_scratch(list(o)[:16], want, o[16])
+
+
+def test_groups_signers_is_the_one_condition(lib):
+    """From 16,384 signatures up, not prestaged, more than one key, at least 4 signatures per key."""
+    for nkeys, pre, nsigs, want in [(4, 0, 16384, 1), (4, 0, 16383, 0), (4, 1, 16384, 0), (1, 0, 20000, 0),
+                                    (0, 0, 20000, 0), (100000, 0, 62500, 0), (100000, 0, 399999, 0),
+                                    (100000, 0, 400000, 1), (8, 0, 16385, 1)]:
+        assert lib.t_groups_signers(_sz(nkeys), pre, _sz(nsigs)) == want, (nkeys, pre, nsigs)
+
+
+@pytest.mark.parametrize("n", [s for s, _ in SCRATCH_SHAPES])
+def test_var_scratch(lib, n):
+    o = _sizes(6)
+    lib.t_var_scratch(_sz(n), o)
+    check_scratch(list(o)[:5], [n * 4 + 4, n * 4 + 4, n * PBUF_WORDS * 4 + 16, n * 40 + 16, n * 320 * 4 + 16], o[5])
+
+
+@pytest.mark.parametrize("S,C,V", [(3, 1, 67), (20000, 200, 20000)])
+def test_core_reservation_is_the_larger_pass(lib, S, C, V):
+    for nkeys in (4, 100000):
+        o = _sizes(5)
+        lib.t_core_scratch(_sz(S), _sz(C), _sz(V), _sz(nkeys), o)
+        total, strict, certs, s_staged, c_staged = list(o)
+        assert (s_staged, c_staged) == (int(S <= 16384), int(V <= 16384))
+        grp = [int(not staged and n >= 16384 and n >= 4 * nkeys) for staged, n in ((s_staged, S), (c_staged, V))]
+        assert strict == sum(align256(w) for w in _cert_scratch_bytes(1, S, 0, grp[0], nkeys, 1))
+        assert certs == sum(align256(w) for w in _cert_scratch_bytes(C, V, 1, grp[1], nkeys, 1))
+        assert total == max(strict, certs)
 
 
 # ---------------------------------------------------------------- MSM plan
@@ -332,6 +454,22 @@ def test_msm_plan_invariants(lib, counts):
     assert p["one"] == int(one)
     m = p["meta"]
     check_block(m[:6], [nb * 4, nb * 4, nsig * 4 + 4, (nb * NA + 1) * 4, len(tasks) * 16 + 16, nb * 4], m[6])
+
+
+@pytest.mark.parametrize("counts", [[3], [511], [512], [3, 520]], ids=str)
+def test_msm_scratch(lib, counts):
+    p = _msm(lib, counts)
+    nb, nsig, ntasks = len(counts), sum(counts), len(p["tasks"])
+    assert p["C"] == (8 if max(counts) >= 512 else 7)
+    buckets = 1 << (p["C"] - 1)
+    ent_words, pt_words, zs_words = 32, 40, 12
+    o = _sizes(9)
+    lib.t_msm_scratch(_p(_u32(counts)), _sz(nb), _sz(nsig), o)
+    assert o[8] == p["meta"][6]                                      # the meta segment holds MsmMetaLayout
+    want = [p["meta"][6], 2 * nsig * ent_words * 4 + 16, p["NA"] * 2 * nsig * 2 + 16, zs_words * nsig * 4 + 16,
+            ntasks * buckets * pt_words * 4 + 16, ntasks * 128 * pt_words * 4 + 16,
+            (ntasks + nb * p["NA"]) * pt_words * 4 + 16]             # meta ent dig zs bkt part wpart
+    check_scratch(list(o)[:7], want, o[7])
 
 
 def test_msm_one_task_windows_boundary(lib):
