@@ -27,10 +27,14 @@ struct nw_job {
 
 namespace nw {
 
-int enqueue_certs(nw_ctx* ctx, Workspace* ws, const CertCall& c, const CertScratch& s, hipStream_t st) {
+int enqueue_certs(nw_ctx* ctx, Workspace* ws, const CertCall& c, const CertPlan& p, const CertScratch& s,
+                  hipStream_t st) {
     const size_t ncerts = c.ncerts, nsigs = c.nsigs;
     const int msgmode = c.msg_base ? 1 : 0;
     const PreStaged* pre = c.pre;
+    // the caller makes the plan for this call, and the scratch from the plan
+    if (!p.made_for(ncerts, nsigs, ctx->nkeys, c.batch_mode, pre, c.sync_check || c.status) || p.groups() != s.group)
+        return NW_ERR_DEVICE;
     auto at = [&](size_t off, bool have = true) {   // an absent segment (size 0) is a null pointer to the kernels
         return have ? reinterpret_cast<uint32_t*>(ws->scratch.bytes() + off) : nullptr;
     };
@@ -39,14 +43,14 @@ int enqueue_certs(nw_ctx* ctx, Workspace* ws, const CertCall& c, const CertScrat
     uint32_t* sig_cert = pre ? pre->sig_cert : at(s.sig_cert);
     uint32_t* slow_count = pre ? pre->zero4 : at(s.slow_count);
     uint32_t* cert_state = !c.batch_mode ? nullptr : (pre ? pre->cert_state : at(s.cert_state));
-    if (!pre) {
+    if (p.preamble.prep_grid) {
         // Preamble in two launches: sig_cert = NO_CERT, zero the slot counts, the slow-path counter,
         // the certificate states and the status word; expand certificates; histogram signer slots;
         // check the device inputs into the status word.  sync_check: the call waits for that check
         // and returns NW_ERR_ARG before anything else is enqueued.
         if (c.sync_check) d_status = at(s.status);
-        NW_TRY(launch_prep_expand((uint32_t)ncerts, (uint32_t)nsigs, (uint32_t)ctx->nkeys, c.first, c.nv, c.signer,
-                                  sig_cert, slow_count, at(s.counts, s.group), d_status, cert_state, st),
+        NW_TRY(launch_prep_expand(p.preamble, (uint32_t)ncerts, (uint32_t)nsigs, (uint32_t)ctx->nkeys, c.first, c.nv,
+                                  c.signer, sig_cert, slow_count, at(s.counts, s.group), d_status, cert_state, st),
                "k_prep_certs / k_expand_count");
         if (c.sync_check) {   // 16 bytes of h_io: reserved by the caller
             NW_TRY(hipMemcpyAsync(ws->h_io.p, d_status, 4, hipMemcpyDeviceToHost, st), "D2H status");
@@ -92,15 +96,15 @@ int enqueue_certs(nw_ctx* ctx, Workspace* ws, const CertCall& c, const CertScrat
     vp.ok_out = c.batch_mode ? nullptr : c.sig_ok;
     vp.pbuf = at(s.pbuf);
     vp.pre = at(s.pre);
-    if (s.group) {
+    if (p.groups()) {
         vp.perm = at(s.perm);
         vp.pinfo = reinterpret_cast<const uint2*>(at(s.pinfo));
-        NW_TRY(launch_group_scatter((uint32_t)nsigs, (uint32_t)ctx->nkeys, c.signer, sig_cert, at(s.counts),
+        NW_TRY(launch_group_scatter(p.group, (uint32_t)nsigs, (uint32_t)ctx->nkeys, c.signer, sig_cert, at(s.counts),
                                     at(s.cursor), at(s.perm), reinterpret_cast<uint2*>(at(s.pinfo)), st),
                "signer grouping");
     }
     vp.gn = (uint32_t)nsigs;   // every column, from g0 = 0
-    vp.fk = finish_k_for(ctx->finish_k, nsigs);
+    vp.fk = p.finish.fk;
     hipEvent_t ev_stop = nullptr;
     {
         std::lock_guard<std::mutex> g(ctx->prof_mu);
@@ -117,13 +121,12 @@ int enqueue_certs(nw_ctx* ctx, Workspace* ws, const CertCall& c, const CertScrat
             ctx->prof_sigs += nsigs;
         }
     }
-    NW_TRY(launch_verify(vp, msgmode, ctx->key_window, st), "k_verify");
-    // brackets k_verify alone, or k_verify_split + the finish fused into it (split_fuses_finish:
-    // launches of <= 4,096 signatures; nwcrypto.h, nw_profile_read)
+    if (p.verify.grid) NW_TRY(launch_verify(vp, p.verify, msgmode, ctx->key_window, st), "k_verify");
+    // brackets k_verify alone, or k_verify_split + the finish fused into it (VerifyPlan::SPLIT_FUSED; nwcrypto.h,
+    // nw_profile_read), which then has done k_finish's work itself (FinishPlan::NONE)
     if (ev_stop) NW_TRY(hipEventRecord(ev_stop, st), "hipEventRecord");
-    // small launches: k_verify_split has done k_finish's work itself (split_fuses_finish)
-    if (!split_fuses_finish(vp.gn, vp.fk)) NW_TRY(launch_finish(vp, st), "k_finish");
-    if (!c.batch_mode) return NW_OK;   // strict verdicts only (bytes written by k_finish): no certificate pass
+    if (p.finish.form != FinishPlan::NONE) NW_TRY(launch_finish(vp, p.finish, st), "k_finish");
+    if (p.tail.form == TailPlan::NONE) return NW_OK;   // strict verdicts only (bytes written by the finish)
 
     FinalizeParams fp{};
     fp.ncerts = (uint32_t)ncerts;
@@ -142,12 +145,12 @@ int enqueue_certs(nw_ctx* ctx, Workspace* ws, const CertCall& c, const CertScrat
     fp.sig_ok = c.sig_ok;
     fp.exact_count = slow_count + 1;   // word 1 of the zeroed slow-path counter block
     fp.exact_list = at(s.exact);
-    if (slow_tail_fits(ncerts, nsigs)) {   // one header / vote batch: exact path + finalize in one launch
-        NW_TRY(launch_slow_tail(vp, fp, msgmode, ctx->key_window, st), "k_slow_tail");
+    if (p.tail.form == TailPlan::SLOW_TAIL) {   // one header / vote batch: exact path + finalize in one launch
+        NW_TRY(launch_slow_tail(vp, fp, p.tail, msgmode, ctx->key_window, st), "k_slow_tail");
         return NW_OK;
     }
-    NW_TRY(launch_slow(vp, msgmode, ctx->key_window, (uint32_t)nsigs, st), "k_slow_prep / k_slow_mul");
-    NW_TRY(launch_finalize(fp, st), "k_cert_finalize / k_cert_exact");
+    if (p.tail.slow_prep_grid) NW_TRY(launch_slow(vp, p.tail, msgmode, ctx->key_window, st), "k_slow_prep / mul");
+    if (p.tail.finalize_grid) NW_TRY(launch_finalize(fp, p.tail, st), "k_cert_finalize / k_cert_exact");
     return NW_OK;
 }
 
@@ -158,13 +161,13 @@ namespace {
 // Strict verify of signatures whose keys are not cached: k_verify_var + k_finish over the uploaded
 // messages, sigs and raw keys (layout l at d_in) and the reserved scratch layout s.
 int enqueue_strict_var(nw_ctx* ctx, Workspace* ws, size_t n, const uint8_t* d_in, const SigKeysLayout& l,
-                       const VarScratch& s, hipStream_t st, uint8_t* d_ok) {
+                       const VarPlan& p, const VarScratch& s, hipStream_t st, uint8_t* d_ok) {
     auto at = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws->scratch.bytes() + off); };
     NW_TRY(hipMemsetAsync(at(s.sig_cert), 0, n * 4 + 4, st), "memset sig_cert");
     VerifyParams vp{};
     vp.n = (uint32_t)n;
     vp.gn = (uint32_t)n;
-    vp.fk = finish_k_for(ctx->finish_k, n);
+    vp.fk = p.finish.fk;
     vp.sig = d_in + l.sig;
     vp.sig_keys = reinterpret_cast<const uint32_t*>(d_in + l.keys);
     vp.sig_cert = at(s.sig_cert);
@@ -176,8 +179,8 @@ int enqueue_strict_var(nw_ctx* ctx, Workspace* ws, size_t n, const uint8_t* d_in
     vp.pbuf = at(s.pbuf);
     vp.pre = at(s.pre);
     vp.ok_out = d_ok;   // verdict bytes straight from k_finish
-    NW_TRY(launch_verify_var(vp, 1, at(s.var), st), "k_verify_var");
-    NW_TRY(launch_finish(vp, st), "k_finish");
+    if (p.grid) NW_TRY(launch_verify_var(vp, 1, p.quad, p.grid, at(s.var), st), "k_verify_var");
+    if (p.finish.grid) NW_TRY(launch_finish(vp, p.finish, st), "k_finish");
     return NW_OK;
 }
 
@@ -264,7 +267,8 @@ int enqueue_staged(nw_ctx* ctx, Workspace* ws, hipStream_t st, CertCall& cc, con
                    const uint8_t* const* msg, const size_t* len, const uint32_t* signer, const uint8_t (*sig)[64],
                    bool want_sig_ok) {
     const size_t nb = cc.ncerts, nsigs = cc.nsigs, total = message_bytes(len, nsigs);
-    const CertScratch cs = cert_scratch(ctx, nb, nsigs, cc.batch_mode, false, true);
+    const CertPlan plan = cert_plan(ctx, nb, nsigs, cc.batch_mode, false);
+    const CertScratch cs(plan, true);
     const StagedLayout l(total, nsigs, nb);
     Stager sg(ctx, ws, st);
     NW_RC(sg.reserve(l.in.end, l.out.end, cs.bytes()));
@@ -283,7 +287,7 @@ int enqueue_staged(nw_ctx* ctx, Workspace* ws, hipStream_t st, CertCall& cc, con
     cc.msg_len = reinterpret_cast<const uint64_t*>(d + l.msgs + l.ml.len);
     cc.cert_ok = d + l.in.end + l.cert_ok;
     cc.sig_ok = want_sig_ok ? d + l.in.end + l.ok : nullptr;   // verdict bytes from k_cert_finalize
-    return enqueue_certs(ctx, ws, cc, cs, st);
+    return enqueue_certs(ctx, ws, cc, plan, cs, st);
 }
 
 // Shared body of strict_many / verify_batch: every signature in one "certificate" 0.  Cached keys
@@ -316,6 +320,7 @@ int run_generic(nw_ctx* ctx, const uint8_t* const* msg, const size_t* len, const
         NW_RC(run_msm(ctx, ws, st, mc, msg, len, pk, sig));
         cc.cert_ok = mc.out;
     } else if (!cached) {
+        const VarPlan vplan(n, ctx->finish_k);
         const VarScratch vs(n);
         const SigKeysLayout l(total, n);
         Stager sg(ctx, ws, st);
@@ -324,12 +329,13 @@ int run_generic(nw_ctx* ctx, const uint8_t* const* msg, const size_t* len, const
         NW_RC(sg.put(l.sig, sig, n * 64, "H2D sig"));
         NW_RC(sg.put(l.keys, pk, n * 32, "H2D keys"));
         cc.sig_ok = sg.dev(l.in.end);
-        NW_RC(enqueue_strict_var(ctx, ws, n, sg.dev(0), l, vs, st, cc.sig_ok));
+        NW_RC(enqueue_strict_var(ctx, ws, n, sg.dev(0), l, vplan, vs, st, cc.sig_ok));
     } else if (small_call(n, total)) {
         // one-message paths (Signature::verify, one certificate's verify_batch): every input and the
         // preamble state in ONE staged H2D, no preamble kernels, both outputs in ONE D2H
         const PackedLayout l(total, n);
-        const CertScratch cs = cert_scratch(ctx, 1, n, batch_mode, true, true);
+        const CertPlan plan = cert_plan(ctx, 1, n, batch_mode, true);
+        const CertScratch cs(plan, true);
         NW_TRY(ws->reserve(l.in.end + l.out.end, cs.bytes(), std::max(l.in.end, l.out.end)), "workspace");
         uint8_t* h = ws->h_io.bytes();
         uint8_t* d = ws->io.bytes();
@@ -362,7 +368,7 @@ int run_generic(nw_ctx* ctx, const uint8_t* const* msg, const size_t* len, const
         cc.pre = &pre;
         cc.cert_ok = d_out + l.cert_ok;
         cc.sig_ok = ok_out ? d_out + l.ok : nullptr;
-        NW_RC(enqueue_certs(ctx, ws, cc, cs, st));
+        NW_RC(enqueue_certs(ctx, ws, cc, plan, cs, st));
         // the H2D above has completed in stream order before this copy overwrites the staging buffer
         NW_TRY(hipMemcpyAsync(h, d_out, l.out.end, hipMemcpyDeviceToHost, st), "D2H outputs");
         NW_RC(call.finish());
@@ -595,7 +601,8 @@ int nw_verify_certs(nw_ctx* ctx, const nw_cert* certs, size_t ncerts, const uint
     // also carry the preamble state (no preamble kernels) and go up in one H2D.  The signature array
     // of a large call goes up in 4 MiB chunks, each DMA overlapping the staging memcpy of the next.
     const CertsLayout l(nsigs, ncerts);
-    const CertScratch cs = cert_scratch(ctx, ncerts, nsigs, 1, l.staged, true);
+    const CertPlan plan = cert_plan(ctx, ncerts, nsigs, 1, l.staged);
+    const CertScratch cs(plan, true);
     NW_TRY(ws->reserve(l.in.end + l.out.end, cs.bytes(), std::max(l.in.end, l.out.end)), "workspace");
     uint8_t* h = ws->h_io.bytes();
     uint8_t* d_in = ws->io.bytes();
@@ -630,7 +637,7 @@ int nw_verify_certs(nw_ctx* ctx, const nw_cert* certs, size_t ncerts, const uint
     cc.cert_ok = d_out + l.cert_ok;
     cc.stake = reinterpret_cast<uint64_t*>(d_out + l.stake);
     cc.sig_ok = sig_ok && nsigs ? d_out + l.ok : nullptr;
-    NW_RC(enqueue_certs(ctx, ws, cc, cs, st));   // on failure the lease synchronizes the stream (the H2D may be in flight)
+    NW_RC(enqueue_certs(ctx, ws, cc, plan, cs, st));   // on failure the lease synchronizes the stream (the H2D may be in flight)
     // the H2D above has completed in stream order before this copy overwrites the staging buffer
     NW_TRY(hipMemcpyAsync(h, d_out, l.out.end, hipMemcpyDeviceToHost, st), "D2H outputs");
     NW_RC(call.finish());
@@ -708,9 +715,10 @@ int nw_verify_certs_dev(nw_ctx* ctx, size_t ncerts, const uint32_t* d_cert_first
     cc.status = d_status;
     // a block that a pending call on this stream still reads is only freed after it (Workspace::ensure)
     Workspace* ws = lease.ws();
-    const CertScratch cs = cert_scratch(ctx, ncerts, nsigs, 1, false, !d_sig_flags);
+    const CertPlan plan = cert_plan(ctx, ncerts, nsigs, 1, false, true);   // the preamble checks the device inputs
+    const CertScratch cs(plan, !d_sig_flags);
     NW_TRY(ws->reserve(0, cs.bytes(), cc.sync_check ? 16 : 0), "workspace");
-    int rc = enqueue_certs(ctx, ws, cc, cs, st);
+    int rc = enqueue_certs(ctx, ws, cc, plan, cs, st);
     if (rc == NW_ERR_ARG) {
         lease.synced();
         return rc;

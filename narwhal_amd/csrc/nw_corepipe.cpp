@@ -51,7 +51,7 @@ int nw_core_batch_verify(nw_ctx* ctx, const nw_core_batch* b, const uint8_t zsee
     hipStream_t st = call.st;
     const CoreLayout l(n, D, b->pre.size(), H, S, C, V);
     // the two signature passes lay their scratch over one block, sized for the larger
-    const CoreScratch cs(l, S, C, V, ctx->nkeys);
+    const CoreScratch cs(l, S, C, V, ctx->nkeys, ctx->finish_k);
     NW_TRY(ws->reserve(l.device_bytes(), cs.bytes(), l.pinned_bytes()), "workspace");
     // one staging pass over the struct of arrays
     uint8_t* h = ws->h_io.bytes();
@@ -123,7 +123,7 @@ int nw_core_batch_verify(nw_ctx* ctx, const nw_core_batch* b, const uint8_t zsee
         cc.batch_mode = 0;
         cc.pre = l.s_staged ? &spre : nullptr;
         cc.sig_ok = d_work + l.sok;
-        NW_RC(enqueue_certs(ctx, ws, cc, cs.strict, st));
+        NW_RC(enqueue_certs(ctx, ws, cc, cs.strict_plan, cs.strict, st));
     }
     // 5. certificate pass: certificate j draws its coefficients at batch index cert_base + j
     if (C) {
@@ -140,7 +140,7 @@ int nw_core_batch_verify(nw_ctx* ctx, const nw_core_batch* b, const uint8_t zsee
         cc.batch_mode = 1;
         cc.pre = l.c_staged ? &cpre : nullptr;
         cc.cert_ok = d_work + l.cok;
-        NW_RC(enqueue_certs(ctx, ws, cc, cs.certs, st));
+        NW_RC(enqueue_certs(ctx, ws, cc, cs.certs_plan, cs.certs, st));
     }
     // 6. verdicts
     CoreVerdictParams vp{};

@@ -300,14 +300,17 @@ struct CertCall {
     uint32_t *flags = nullptr, *status = nullptr;   // flags null: workspace scratch
     uint64_t* stake = nullptr;
 };
-// Scratch layout of a run against this context's key cache (shared key lock held); prestaged: CertCall::pre set.
-inline CertScratch cert_scratch(const nw_ctx* ctx, size_t ncerts, size_t nsigs, uint32_t batch_mode, bool prestaged,
-                                bool own_flags) {
-    return CertScratch(ncerts, nsigs, batch_mode, groups_signers(ctx->nkeys, prestaged, nsigs), ctx->nkeys, own_flags);
+// Launch plan of a run against this context's key cache (shared key lock held), built once before the
+// call's reservation: it sizes the scratch (CertScratch(plan, own_flags)) and enqueue_certs walks it.
+// prestaged: CertCall::pre set; status: CertCall::sync_check or CertCall::status set.
+inline CertPlan cert_plan(const nw_ctx* ctx, size_t ncerts, size_t nsigs, uint32_t batch_mode, bool prestaged,
+                          bool status = false) {
+    return CertPlan(ncerts, nsigs, ctx->nkeys, batch_mode, prestaged, status, ctx->finish_k);
 }
-// Enqueue the certificate pipeline on st (shared key lock held, workspace bound to st) over the
-// scratch layout s, which the caller has reserved; allocates nothing.
-int enqueue_certs(nw_ctx* ctx, Workspace* ws, const CertCall& c, const CertScratch& s, hipStream_t st);
+// Enqueue the certificate pipeline on st (shared key lock held, workspace bound to st): the launches
+// of plan p over the scratch layout s made from it, which the caller has reserved; allocates nothing.
+int enqueue_certs(nw_ctx* ctx, Workspace* ws, const CertCall& c, const CertPlan& p, const CertScratch& s,
+                  hipStream_t st);
 
 // Wait for every call that may still read the key tables (exclusive key lock held).
 int drain_all(nw_ctx* ctx);

@@ -2,7 +2,8 @@
 // touches the GPU.  Range validation, the staging-buffer layouts (each defined once: the same
 // definition gives the byte count that sizes a buffer and the offsets that fill it), the preamble
 // state of a small call, the MSM task plan, the asynchronous digest's chunk boundaries, the key comb
-// window and the k_finish lane depth.  No runtime call: compiles for the host alone (hipcc
+// window, the k_finish lane depth and the launch plan: which kernels run, in which form, over which
+// grid.  No runtime call: compiles for the host alone (hipcc
 // --cuda-host-only, or g++ with the ROCm include path) and is tested on the CPU
 // (tests/test_host_plan.py).
 #pragma once
@@ -10,6 +11,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
+#include <initializer_list>
 #include <utility>
 #include <vector>
 
@@ -161,6 +163,136 @@ inline bool groups_signers(size_t nkeys, bool prestaged, size_t nsigs) {
     return NW_GROUP_SIGNERS && !prestaged && nsigs >= kGroupMinSigs && nkeys > 1 && nsigs >= kGroupMinSigsPerKey * nkeys;
 }
 
+// Signatures per k_finish lane for a launch of n (``fixed``: a pinned value, 0 = adaptive): just
+// enough that the lanes fit one wave per SIMD, because below that the kernel is bound by the serial
+// prefix-product chain + inversion of each lane, not by the inversion count.  k_finish<ONE> up to
+// one lane per SIMD slot (256 CUs x 4 SIMDs x 64); above, the chunked kernel (four waves per SIMD)
+// with the fewest signatures per lane (2 .. FINISH_K) that still fits the chip in one round.  A
+// single certificate (67 .. 6,667 signatures) gets one signature per lane: one inversion per
+// signature, no chain; C2's million signatures get 16 per lane.
+inline uint32_t finish_k_for(uint32_t fixed, size_t n) {
+    if (fixed) return fixed;
+    const size_t one_max = 256 * 4 * 64, lanes = one_max * 4;
+    if (n <= one_max) return 1;
+    const size_t k = (n + lanes - 1) / lanes;
+    return k < 2 ? 2u : (k > (size_t)FINISH_K ? (uint32_t)FINISH_K : (uint32_t)k);
+}
+
+// ------------------------------------------------------------------------------------ launch plan
+// Which kernels a call launches, in which form and with which grid.  The launchers (nw_kernels.h)
+// execute the parts below and decide nothing; DESIGN.md's shape -> plan table restates this section.
+// Every grid is a block count, 0 when the stage is not launched.
+
+// k_verify_split does k_finish's work itself: no k_finish launch.
+inline bool split_fuses_finish(size_t n, uint32_t fk) { return n <= SPLIT_FUSE_MAX_SIGS && fk == 1; }
+// The whole exact path and the finalize in one workgroup (k_slow_tail).
+inline bool slow_tail_fits(size_t ncerts, size_t nsigs) {
+    return ncerts >= 1 && ncerts <= TAIL_MAX_CERTS && nsigs >= 1 && nsigs <= SLOW_TAIL_MAX_SIGS;
+}
+
+// k_finish over n signatures; may_fuse: the verify kernel ahead of it is k_verify_split.
+inline FinishPlan finish_plan(uint32_t pinned_fk, size_t n, bool may_fuse) {
+    FinishPlan f;
+    f.fk = finish_k_for(pinned_fk, n);
+    if (n == 0 || (may_fuse && split_fuses_finish(n, f.fk))) return f;
+    const uint64_t lanes = ((uint64_t)n + f.fk - 1) / f.fk;
+    f.form = f.fk == 1 ? FinishPlan::ONE : FinishPlan::CHUNKED;
+    f.grid = blocks_for(lanes, f.fk == 1 ? 256 : FINISH_WG);
+    return f;
+}
+
+// One run of the certificate pipeline (enqueue_certs) over ncerts certificates and nsigs
+// signatures against a cache of nkeys keys.  prestaged: the caller uploaded the preamble state
+// (PreLayout); status: the preamble checks the device inputs into a status word; pinned_fk:
+// nw_ctx::finish_k (0: adaptive).
+struct CertPlan {
+    size_t ncerts, nsigs, nkeys;
+    uint32_t batch_mode;
+    bool prestaged, status;
+    PreamblePlan preamble;
+    GroupPlan group;
+    VerifyPlan verify;
+    FinishPlan finish;
+    TailPlan tail;
+
+    CertPlan(size_t ncerts, size_t nsigs, size_t nkeys, uint32_t batch_mode, bool prestaged, bool status,
+             uint32_t pinned_fk)
+        : ncerts(ncerts), nsigs(nsigs), nkeys(nkeys), batch_mode(batch_mode), prestaged(prestaged),
+          status(status) {
+        const bool groups = groups_signers(nkeys, prestaged, nsigs);
+        const bool lds_keys = nkeys <= GROUP_LDS_KEYS;
+        if (!prestaged) {
+            preamble.prep_grid = std::min(blocks_for(std::max(nsigs + 1, ncerts), 256), 1024u);
+            // waves per certificate from the average vote count (a performance choice only); the
+            // same grid covers the signature tiles when slots are counted (grouping) or checked
+            const size_t avg_votes = ncerts ? nsigs / ncerts : 0;
+            preamble.expand_wlog = avg_votes > 512 ? 2u : (avg_votes > 128 ? 1u : 0u);
+            const bool tiles = (groups || status) && nsigs > 0;
+            preamble.expand_grid = std::max(blocks_for(ncerts, EXPAND_WAVES_PER_BLOCK >> preamble.expand_wlog),
+                                            tiles ? blocks_for(nsigs, GROUP_TILE) : 0u);
+            preamble.expand_lds = groups && lds_keys ? (uint32_t)nkeys * 4 : 0;
+        }
+        if (groups) {   // nsigs >= kGroupMinSigs, nkeys > 1
+            group.form = lds_keys ? GroupPlan::LDS : GroupPlan::GLOBAL;
+            group.scan_grid = 1;
+            group.scatter_grid = blocks_for(nsigs, lds_keys ? GROUP_TILE : 256);
+            group.scatter_lds = lds_keys ? (uint32_t)nkeys * 8 : 0;
+        }
+        const bool split = nsigs <= VERIFY_SPLIT_MAX_SIGS;
+        finish = finish_plan(pinned_fk, nsigs, split);
+        if (nsigs) {
+            verify.form = !split ? VerifyPlan::FULL
+                                 : (finish.form == FinishPlan::NONE ? VerifyPlan::SPLIT_FUSED : VerifyPlan::SPLIT);
+            verify.grid = blocks_for(split ? (uint64_t)nsigs * VERIFY_SPLIT : nsigs, 256);
+        }
+        if (!batch_mode) return;   // strict verdicts only, written by the finish
+        if (slow_tail_fits(ncerts, nsigs)) {
+            tail.form = TailPlan::SLOW_TAIL;
+            tail.slow_tail_grid = 1;
+            return;
+        }
+        tail.form = TailPlan::GRID;
+        if (nsigs) {   // grid-stride over the device slow list, one block per CU at the most
+            tail.slow_prep_grid = std::min(blocks_for(nsigs, 256), SLOW_MAX_BLOCKS);
+            tail.slow_mul_grid = std::min(blocks_for(nsigs, SLOW_MUL_QUADS), SLOW_MAX_BLOCKS);
+        }
+        if (!ncerts) return;
+        if (ncerts <= TAIL_MAX_CERTS && nsigs <= CERT_TAIL_MAX_SIGS) {   // finalize + exact sum in one wave
+            tail.finalize = TailPlan::CERT_TAIL;
+            tail.finalize_grid = 1;
+            return;
+        }
+        const size_t avg_votes = nsigs / ncerts;
+        tail.finalize = avg_votes > 1024 ? TailPlan::WG1024 : (avg_votes > 256 ? TailPlan::WG256 : TailPlan::WAVE);
+        // a wave per certificate, or a workgroup
+        tail.finalize_grid = tail.finalize == TailPlan::WAVE ? blocks_for((uint64_t)ncerts * 64, 256) : (uint32_t)ncerts;
+        tail.exact_grid = (uint32_t)std::min<size_t>(ncerts, EXACT_MAX_BLOCKS);
+    }
+    bool groups() const { return group.form != GroupPlan::OFF; }
+    bool made_for(size_t c, size_t n, size_t k, uint32_t mode, bool pre, bool st) const {
+        return c == ncerts && n == nsigs && k == nkeys && mode == batch_mode && pre == prestaged && st == status;
+    }
+    // kernel launches of the run
+    uint32_t launches() const {
+        uint32_t k = 0;
+        for (uint32_t grid : {preamble.prep_grid, preamble.expand_grid, group.scan_grid, group.scatter_grid, verify.grid,
+                              finish.grid, tail.slow_tail_grid, tail.slow_prep_grid, tail.slow_mul_grid,
+                              tail.finalize_grid, tail.exact_grid})
+            k += grid != 0;
+        return k;
+    }
+};
+
+// The strict variable-base verify (enqueue_strict_var): k_verify_var, then k_finish.
+struct VarPlan {
+    bool quad;
+    uint32_t grid;
+    FinishPlan finish;
+    VarPlan(size_t n, uint32_t pinned_fk)
+        : quad(n <= VAR_QUAD_MAX_SIGS), grid(blocks_for(n, quad ? 16 : 256)), finish(finish_plan(pinned_fk, n, false)) {}
+    uint32_t launches() const { return (grid != 0) + (finish.grid != 0); }
+};
+
 // Device scratch of one run of the certificate pipeline (enqueue_certs).  Segments a run does not
 // use have size 0: the exact-path state without batch_mode, the grouping tables without ``group``,
 // the flags when the caller supplies its own.  The run writes every word before it reads it.
@@ -179,16 +311,19 @@ struct CertScratch {
           exact(b.take(batch_mode ? ncerts * 4 + 16 : 0)), counts(b.take(group ? nkeys * 4 + 16 : 0)),
           cursor(b.take(group ? nkeys * 4 + 16 : 0)), perm(b.take(group ? nsigs * 4 + 16 : 0)),
           pinfo(b.take(group ? nsigs * 8 + 16 : 0)) {}
+    CertScratch(const CertPlan& p, bool own_flags)
+        : CertScratch(p.ncerts, p.nsigs, p.batch_mode, p.groups(), p.nkeys, own_flags) {}
     size_t bytes() const { return b.end; }
 };
 
 // The two passes of a mixed Core batch lay their scratch over one block, sized for the larger: they
 // are serial in stream order and everything they keep lives in the CoreLayout block.
 struct CoreScratch {
+    CertPlan strict_plan, certs_plan;   // the launch plans of the two passes; each sizes its scratch
     CertScratch strict, certs;
-    CoreScratch(const CoreLayout& l, size_t S, size_t C, size_t V, size_t nkeys)
-        : strict(1, S, 0, groups_signers(nkeys, l.s_staged, S), nkeys, true),
-          certs(C, V, 1, groups_signers(nkeys, l.c_staged, V), nkeys, true) {}
+    CoreScratch(const CoreLayout& l, size_t S, size_t C, size_t V, size_t nkeys, uint32_t pinned_fk = 0)
+        : strict_plan(1, S, nkeys, 0, l.s_staged, false, pinned_fk),
+          certs_plan(C, V, nkeys, 1, l.c_staged, false, pinned_fk), strict(strict_plan, true), certs(certs_plan, true) {}
     size_t bytes() const { return std::max(strict.bytes(), certs.bytes()); }
 };
 
@@ -343,21 +478,6 @@ int committee_window(size_t n, double headroom, size_t budget, TableWords table_
         if (need <= (double)budget) return w;
     }
     return 8;
-}
-
-// Signatures per k_finish lane for a launch of n (``fixed``: a pinned value, 0 = adaptive): just
-// enough that the lanes fit one wave per SIMD, because below that the kernel is bound by the serial
-// prefix-product chain + inversion of each lane, not by the inversion count.  k_finish<ONE> up to
-// one lane per SIMD slot (256 CUs x 4 SIMDs x 64); above, the chunked kernel (four waves per SIMD)
-// with the fewest signatures per lane (2 .. FINISH_K) that still fits the chip in one round.  A
-// single certificate (67 .. 6,667 signatures) gets one signature per lane: one inversion per
-// signature, no chain; C2's million signatures get 16 per lane.
-inline uint32_t finish_k_for(uint32_t fixed, size_t n) {
-    if (fixed) return fixed;
-    const size_t one_max = 256 * 4 * 64, lanes = one_max * 4;
-    if (n <= one_max) return 1;
-    const size_t k = (n + lanes - 1) / lanes;
-    return k < 2 ? 2u : (k > (size_t)FINISH_K ? (uint32_t)FINISH_K : (uint32_t)k);
 }
 
 }  // namespace nw

@@ -45,7 +45,21 @@ static constexpr int FINISH_K = NW_FINISH_K;      // signatures per lane in the 
 // Verify launches of at most this many signatures with one signature per k_finish lane (fk = 1) run
 // k_verify_split with k_finish's work fused in (nw_verify_split.h): no k_finish launch.
 static constexpr uint32_t SPLIT_FUSE_MAX_SIGS = 4096;
-inline bool split_fuses_finish(uint32_t gn, uint32_t fk) { return gn <= SPLIT_FUSE_MAX_SIGS && fk == 1; }
+
+// Launch geometry the host plan decides with (nw_host_plan.h: CertPlan) and the kernels are written
+// against; each is explained, and checked by a static_assert where it matters, next to its kernel.
+static constexpr uint32_t VERIFY_SPLIT_MAX_SIGS = 16384;   // k_verify_split up to here, k_verify above
+static constexpr int VERIFY_SPLIT = 8;                     // k_verify_split lanes per signature
+#ifndef NW_GROUP_TILE
+#define NW_GROUP_TILE 4096
+#endif
+static constexpr uint32_t GROUP_TILE = NW_GROUP_TILE;      // signatures per histogram / scatter tile
+static constexpr uint32_t GROUP_LDS_KEYS = 8192;           // key-cache slots up to which the tile's tables sit in LDS
+static constexpr uint32_t FINISH_WG = 256;                 // chunked k_finish workgroup
+static constexpr uint32_t SLOW_MAX_BLOCKS = 256;           // k_slow_prep / k_slow_mul grid cap: one block per CU
+static constexpr uint32_t SLOW_MUL_QUADS = 64;             // k_slow_mul entries per 256-thread workgroup
+static constexpr uint32_t EXACT_MAX_BLOCKS = 1024;         // k_cert_exact grid cap
+static constexpr uint32_t EXPAND_WAVES_PER_BLOCK = 4;      // k_expand_count: certificates per block at wlog 0
 
 static inline unsigned blocks_for(uint64_t n, unsigned t) { return (unsigned)((n + t - 1) / t); }
 
@@ -106,32 +120,58 @@ struct FinalizeParams {
     uint32_t* exact_list;          // [ncerts] ... certificates whose verdict needs the exact sum (k_cert_exact)
 };
 
-hipError_t launch_verify(const VerifyParams& p, int msgmode, int key_window, hipStream_t st);
-hipError_t launch_finish(const VerifyParams& p, hipStream_t st);
+// One run of the certificate pipeline as the host plan lays it out: per stage the kernel form and
+// its grid (0: not launched).  Plain data: every decision is CertPlan's (nw_host_plan.h); the
+// launchers below execute the part they are handed and decide nothing.
+struct PreamblePlan {
+    uint32_t prep_grid = 0;                                  // k_prep_certs
+    uint32_t expand_grid = 0, expand_wlog = 0, expand_lds = 0;   // k_expand_count: 2^wlog waves per certificate
+};
+struct GroupPlan {
+    enum Form : uint32_t { OFF, LDS, GLOBAL } form = OFF;   // k_scatter_slots_lds | k_scatter_slots
+    uint32_t scan_grid = 0, scatter_grid = 0, scatter_lds = 0;
+};
+struct VerifyPlan {
+    enum Form : uint32_t { SKIP, SPLIT_FUSED, SPLIT, FULL } form = SKIP;   // k_verify_split<FUSE> | k_verify
+    uint32_t grid = 0;
+};
+struct FinishPlan {
+    enum Form : uint32_t { NONE, ONE, CHUNKED } form = NONE;   // fused into the verify | k_finish<true> | <false>
+    uint32_t fk = 1, grid = 0;
+};
+struct TailPlan {
+    enum Form : uint32_t { NONE, SLOW_TAIL, GRID } form = NONE;   // strict-only | k_slow_tail | the kernels below
+    enum Finalize : uint32_t { F_NONE, CERT_TAIL, WAVE, WG256, WG1024 } finalize = F_NONE;
+    uint32_t slow_tail_grid = 0;                             // SLOW_TAIL: the one workgroup
+    uint32_t slow_prep_grid = 0, slow_mul_grid = 0;          // GRID
+    uint32_t finalize_grid = 0, exact_grid = 0;              // GRID; k_cert_tail does both in one wave
+};
+
+hipError_t launch_verify(const VerifyParams& p, const VerifyPlan& v, int msgmode, int key_window, hipStream_t st);
+hipError_t launch_finish(const VerifyParams& p, const FinishPlan& f, hipStream_t st);
 // Exact path of the batch equation: k_slow_prep (every signature with D_i != O: decode R, D_i,
 // small-order test) then k_slow_mul (z_i D_i, only for certificates with two or more SK_BIG
 // entries); both read the device slow counter, so honest batches find no work.
-hipError_t launch_slow(const VerifyParams& p, int msgmode, int key_window, uint32_t n_upper, hipStream_t st);
-hipError_t launch_finalize(const FinalizeParams& p, hipStream_t st);
+hipError_t launch_slow(const VerifyParams& p, const TailPlan& t, int msgmode, int key_window, hipStream_t st);
+hipError_t launch_finalize(const FinalizeParams& p, const TailPlan& t, hipStream_t st);
 // Calls of at most TAIL_MAX_CERTS certificates finalize in one wave (k_cert_tail); with at most
 // SLOW_TAIL_MAX_SIGS signatures as well, the whole exact path and the finalize run in one workgroup
 // (k_slow_tail, launch_slow_tail) instead of launch_slow + launch_finalize.
 static constexpr uint32_t TAIL_MAX_CERTS = 16;
 static constexpr uint32_t SLOW_TAIL_MAX_SIGS = 256;
-inline bool slow_tail_fits(uint64_t ncerts, uint64_t nsigs) {
-    return ncerts >= 1 && ncerts <= TAIL_MAX_CERTS && nsigs >= 1 && nsigs <= SLOW_TAIL_MAX_SIGS;
-}
-hipError_t launch_slow_tail(const VerifyParams& p, const FinalizeParams& f, int msgmode, int key_window, hipStream_t st);
+static constexpr uint32_t CERT_TAIL_MAX_SIGS = 64u * 1024u;
+hipError_t launch_slow_tail(const VerifyParams& p, const FinalizeParams& f, const TailPlan& t, int msgmode,
+                            int key_window, hipStream_t st);
 // Batch preamble: reset sig_cert to NO_CERT, zero counts (may be null: no histogram) / the slow
 // counter / status (may be null: no input check), expand certificates (a vote claimed by two
 // certificates is NW_ERR_ARG), histogram + check signer slots (k_prep_certs, k_expand_count); then
 // launch_group_scatter (scan + scatter) when counts were built.
-hipError_t launch_prep_expand(uint32_t ncerts, uint32_t nsigs, uint32_t nkeys, const uint32_t* first,
-                              const uint32_t* nv, const uint32_t* signer, uint32_t* sig_cert, uint32_t* zero4,
-                              uint32_t* counts, uint32_t* status, uint32_t* cert_state, hipStream_t st);
-hipError_t launch_group_scatter(uint32_t n, uint32_t nkeys, const uint32_t* signer, const uint32_t* sig_cert,
-                                const uint32_t* counts, uint32_t* cursor, uint32_t* perm, uint2* pinfo,
-                                hipStream_t st);
+hipError_t launch_prep_expand(const PreamblePlan& pl, uint32_t ncerts, uint32_t nsigs, uint32_t nkeys,
+                              const uint32_t* first, const uint32_t* nv, const uint32_t* signer, uint32_t* sig_cert,
+                              uint32_t* zero4, uint32_t* counts, uint32_t* status, uint32_t* cert_state, hipStream_t st);
+hipError_t launch_group_scatter(const GroupPlan& g, uint32_t n, uint32_t nkeys, const uint32_t* signer,
+                                const uint32_t* sig_cert, const uint32_t* counts, uint32_t* cursor, uint32_t* perm,
+                                uint2* pinfo, hipStream_t st);
 // Tables for nk keys at tab + j * stride (u32 words); negtab: each followed by its negated copy
 // (stride >= 2 comb_words(window)).
 hipError_t launch_key_prep(uint32_t nk, const uint32_t* keys_raw, uint32_t* key_info, uint32_t* bases,

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 #include "nw_point.h"
 #include "nw_sha512.h"
 #include "nw_kernels.h"
@@ -32,19 +33,19 @@
 namespace nw {
 
 template <int WA>
-hipError_t launch_vs_wa(const VerifyParams& p, int msgmode, bool slow, uint32_t n_upper, hipStream_t st);
+hipError_t launch_vs_wa(const VerifyParams& p, int msgmode, bool slow, uint32_t grid, hipStream_t st);
 extern template hipError_t launch_vs_wa<8>(const VerifyParams&, int, bool, uint32_t, hipStream_t);
 extern template hipError_t launch_vs_wa<9>(const VerifyParams&, int, bool, uint32_t, hipStream_t);
 extern template hipError_t launch_vs_wa<12>(const VerifyParams&, int, bool, uint32_t, hipStream_t);
 extern template hipError_t launch_vs_wa<13>(const VerifyParams&, int, bool, uint32_t, hipStream_t);
 extern template hipError_t launch_vs_wa<16>(const VerifyParams&, int, bool, uint32_t, hipStream_t);
 extern template hipError_t launch_vs_wa<20>(const VerifyParams&, int, bool, uint32_t, hipStream_t);
-extern template hipError_t launch_slow_tail_wa<8>(const VerifyParams&, const FinalizeParams&, int, hipStream_t);
-extern template hipError_t launch_slow_tail_wa<9>(const VerifyParams&, const FinalizeParams&, int, hipStream_t);
-extern template hipError_t launch_slow_tail_wa<12>(const VerifyParams&, const FinalizeParams&, int, hipStream_t);
-extern template hipError_t launch_slow_tail_wa<13>(const VerifyParams&, const FinalizeParams&, int, hipStream_t);
-extern template hipError_t launch_slow_tail_wa<16>(const VerifyParams&, const FinalizeParams&, int, hipStream_t);
-extern template hipError_t launch_slow_tail_wa<20>(const VerifyParams&, const FinalizeParams&, int, hipStream_t);
+extern template hipError_t launch_slow_tail_wa<8>(const VerifyParams&, const FinalizeParams&, int, uint32_t, hipStream_t);
+extern template hipError_t launch_slow_tail_wa<9>(const VerifyParams&, const FinalizeParams&, int, uint32_t, hipStream_t);
+extern template hipError_t launch_slow_tail_wa<12>(const VerifyParams&, const FinalizeParams&, int, uint32_t, hipStream_t);
+extern template hipError_t launch_slow_tail_wa<13>(const VerifyParams&, const FinalizeParams&, int, uint32_t, hipStream_t);
+extern template hipError_t launch_slow_tail_wa<16>(const VerifyParams&, const FinalizeParams&, int, uint32_t, hipStream_t);
+extern template hipError_t launch_slow_tail_wa<20>(const VerifyParams&, const FinalizeParams&, int, uint32_t, hipStream_t);
 
 // ------------------------------------------------------------------------------------ signer grouping
 // Counting sort of signature indices by key-cache slot: perm lists the signatures of slot 0, then
@@ -52,12 +53,8 @@ extern template hipError_t launch_slow_tail_wa<20>(const VerifyParams&, const Fi
 // Committees are small next to a batch (100 keys, 1M signatures), so global per-slot atomics would
 // serialize: each workgroup histograms a GROUP_TILE-signature tile in LDS and touches global
 // memory once per (tile, slot).  Above GROUP_LDS_KEYS slots the plain global-atomic form is used
-// (contention is then spread over many addresses anyway).
-#ifndef NW_GROUP_TILE
-#define NW_GROUP_TILE 4096
-#endif
-static constexpr uint32_t GROUP_TILE = NW_GROUP_TILE;
-static constexpr uint32_t GROUP_LDS_KEYS = 8192;
+// (contention is then spread over many addresses anyway).  GROUP_TILE, GROUP_LDS_KEYS: nw_kernels.h.
+static_assert(2 * GROUP_LDS_KEYS * 4 <= 64 * 1024, "k_scatter_slots_lds: two tables of GROUP_LDS_KEYS words in LDS");
 
 // Out-of-range slots (rejected by k_verify) are grouped with slot 0 so no access leaves the arrays.
 __device__ __forceinline__ uint32_t clamp_slot(uint32_t s, uint32_t nkeys) { return s < nkeys ? s : 0u; }
@@ -140,8 +137,7 @@ __global__ void __launch_bounds__(256) k_scatter_slots_lds(uint32_t n, uint32_t 
 // signatures at C4 against 0.56 ms now, 126 against 104 us at C2 (profiles/r06/finish_ab_r06.txt).
 // chunked k_finish workgroup: one inversion each.  512 / 1,024 threads (fewer inversions sharing a
 // CU's scalar unit) measured slower at C2 and C4: 155 / 111 us against 104 us per C2 step
-// (profiles/r06/finish_ab_r06.txt)
-static constexpr uint32_t FINISH_WG = 256;
+// (profiles/r06/finish_ab_r06.txt).  FINISH_WG: nw_kernels.h.
 template <bool ONE>
 __global__ void __launch_bounds__(ONE ? 256 : FINISH_WG) k_finish(VerifyParams a) {
     const uint32_t NL = (a.gn + a.fk - 1) / a.fk;
@@ -244,7 +240,7 @@ __global__ void __launch_bounds__(NT) k_cert_finalize_wg(FinalizeParams a) {
     if (threadIdx.x == 0) finalize_decide(a, c, FinalizeAcc{s_bad != 0u, s_slow != 0u, s_tsum, (uint64_t)s_stake});
 }
 
-static constexpr uint32_t EXACT_MAX_BLOCKS = 1024;
+// Grid-stride over the exact list, at most EXACT_MAX_BLOCKS (nw_kernels.h) one-wave blocks.
 __global__ void __launch_bounds__(64) k_cert_exact(FinalizeParams a) {
     __shared__ uint32_t part[64][40];
     const uint32_t cnt = *a.exact_count;
@@ -286,7 +282,7 @@ __global__ void __launch_bounds__(256) k_prep_certs(uint32_t nsigs, uint32_t nke
     if (status && t == 0) *status = 0u;
 }
 
-static constexpr uint32_t EXPAND_WAVES_PER_BLOCK = 4;
+static_assert(EXPAND_WAVES_PER_BLOCK * 64 == 256, "k_expand_count: a block is EXPAND_WAVES_PER_BLOCK waves");
 __global__ void __launch_bounds__(256) k_expand_count(uint32_t ncerts, uint32_t nsigs, uint32_t nkeys,
                                                       const uint32_t* cert_first, const uint32_t* cert_n,
                                                       const uint32_t* signer, uint32_t* sig_cert, uint32_t* counts,
@@ -348,106 +344,89 @@ __global__ void __launch_bounds__(256) k_slow_mul(VerifyParams a) {
 }
 
 // ------------------------------------------------------------------------------------ launchers
-static hipError_t launch_vs(const VerifyParams& p, int msgmode, int key_window, bool slow, uint32_t n_upper,
-                            hipStream_t st) {
+// Each executes the part of the host plan it is handed (nw_kernels.h; decided by CertPlan,
+// nw_host_plan.h): what is left here is (form, msgmode, key window, key_negtab) -> instantiation.
+template <class F>
+static hipError_t for_window(int key_window, F&& launch) {
     switch (key_window) {
-        case 8: return launch_vs_wa<8>(p, msgmode, slow, n_upper, st);
-        case 9: return launch_vs_wa<9>(p, msgmode, slow, n_upper, st);
-        case 12: return launch_vs_wa<12>(p, msgmode, slow, n_upper, st);
-        case 13: return launch_vs_wa<13>(p, msgmode, slow, n_upper, st);
-        case 16: return launch_vs_wa<16>(p, msgmode, slow, n_upper, st);
-        case 20: return launch_vs_wa<20>(p, msgmode, slow, n_upper, st);
+        case 8: return launch(std::integral_constant<int, 8>{});
+        case 9: return launch(std::integral_constant<int, 9>{});
+        case 12: return launch(std::integral_constant<int, 12>{});
+        case 13: return launch(std::integral_constant<int, 13>{});
+        case 16: return launch(std::integral_constant<int, 16>{});
+        case 20: return launch(std::integral_constant<int, 20>{});
         default: return hipErrorInvalidValue;
     }
 }
 
-hipError_t launch_verify(const VerifyParams& p, int msgmode, int key_window, hipStream_t st) {
-    if (p.gn == 0) return hipSuccess;
-    return launch_vs(p, msgmode, key_window, false, 0, st);
+hipError_t launch_verify(const VerifyParams& p, const VerifyPlan& v, int msgmode, int key_window, hipStream_t st) {
+    return for_window(key_window, [&](auto wa) {
+        constexpr int WA = decltype(wa)::value;
+        if (v.form == VerifyPlan::FULL) return launch_vs_wa<WA>(p, msgmode, false, v.grid, st);
+        return launch_split_wa<WA>(p, msgmode, v.form == VerifyPlan::SPLIT_FUSED, v.grid, st);
+    });
 }
 
-hipError_t launch_slow(const VerifyParams& p, int msgmode, int key_window, uint32_t n_upper, hipStream_t st) {
-    if (n_upper == 0) return hipSuccess;
-    hipError_t e = launch_vs(p, msgmode, key_window, true, n_upper, st);
+hipError_t launch_slow(const VerifyParams& p, const TailPlan& t, int msgmode, int key_window, hipStream_t st) {
+    hipError_t e = for_window(key_window, [&](auto wa) {
+        return launch_vs_wa<decltype(wa)::value>(p, msgmode, true, t.slow_prep_grid, st);
+    });
     if (e != hipSuccess) return e;
-    const uint32_t nb = std::min<uint32_t>(blocks_for(n_upper, SLOW_MUL_QUADS), 256u);
-    hipLaunchKernelGGL(k_slow_mul, dim3(nb), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(k_slow_mul, dim3(t.slow_mul_grid), dim3(256), 0, st, p);
     return hipGetLastError();
 }
 
-hipError_t launch_slow_tail(const VerifyParams& p, const FinalizeParams& f, int msgmode, int key_window,
-                            hipStream_t st) {
-    switch (key_window) {
-        case 8: return launch_slow_tail_wa<8>(p, f, msgmode, st);
-        case 9: return launch_slow_tail_wa<9>(p, f, msgmode, st);
-        case 12: return launch_slow_tail_wa<12>(p, f, msgmode, st);
-        case 13: return launch_slow_tail_wa<13>(p, f, msgmode, st);
-        case 16: return launch_slow_tail_wa<16>(p, f, msgmode, st);
-        case 20: return launch_slow_tail_wa<20>(p, f, msgmode, st);
+hipError_t launch_slow_tail(const VerifyParams& p, const FinalizeParams& f, const TailPlan& t, int msgmode,
+                            int key_window, hipStream_t st) {
+    return for_window(key_window, [&](auto wa) {
+        return launch_slow_tail_wa<decltype(wa)::value>(p, f, msgmode, t.slow_tail_grid, st);
+    });
+}
+
+hipError_t launch_finish(const VerifyParams& p, const FinishPlan& f, hipStream_t st) {
+    if (f.fk != p.fk || p.fk < 1 || p.fk > (uint32_t)FINISH_K || (uint64_t)p.g0 + p.gn > p.n) return hipErrorInvalidValue;
+    if (f.form == FinishPlan::ONE) hipLaunchKernelGGL(k_finish<true>, dim3(f.grid), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(k_finish<false>, dim3(f.grid), dim3(FINISH_WG), 0, st, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_finalize(const FinalizeParams& p, const TailPlan& t, hipStream_t st) {
+    switch (t.finalize) {
+        case TailPlan::CERT_TAIL: hipLaunchKernelGGL(k_cert_tail, dim3(t.finalize_grid), dim3(64), 0, st, p); break;
+        case TailPlan::WG1024: hipLaunchKernelGGL(k_cert_finalize_wg<1024>, dim3(t.finalize_grid), dim3(1024), 0, st, p); break;
+        case TailPlan::WG256: hipLaunchKernelGGL(k_cert_finalize_wg<256>, dim3(t.finalize_grid), dim3(256), 0, st, p); break;
+        case TailPlan::WAVE: hipLaunchKernelGGL(k_cert_finalize, dim3(t.finalize_grid), dim3(256), 0, st, p); break;
         default: return hipErrorInvalidValue;
     }
-}
-
-hipError_t launch_finish(const VerifyParams& p, hipStream_t st) {
-    if (p.gn == 0) return hipSuccess;
-    if (p.fk < 1 || p.fk > (uint32_t)FINISH_K || (uint64_t)p.g0 + p.gn > p.n) return hipErrorInvalidValue;
-    const uint64_t lanes = (p.gn + p.fk - 1) / p.fk;
-    if (p.fk == 1) hipLaunchKernelGGL(k_finish<true>, dim3(blocks_for(lanes, 256)), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(k_finish<false>, dim3(blocks_for(lanes, FINISH_WG)), dim3(FINISH_WG), 0, st, p);
-    return hipGetLastError();
-}
-
-hipError_t launch_finalize(const FinalizeParams& p, hipStream_t st) {
-    if (p.ncerts == 0) return hipSuccess;
-    if (p.ncerts <= TAIL_MAX_CERTS && p.nsigs <= 64u * 1024u) {
-        hipLaunchKernelGGL(k_cert_tail, dim3(1), dim3(64), 0, st, p);
-        return hipGetLastError();
-    }
-    const uint64_t avg_votes = p.nsigs / p.ncerts;
-    if (avg_votes > 1024)
-        hipLaunchKernelGGL(k_cert_finalize_wg<1024>, dim3(p.ncerts), dim3(1024), 0, st, p);
-    else if (avg_votes > 256)
-        hipLaunchKernelGGL(k_cert_finalize_wg<256>, dim3(p.ncerts), dim3(256), 0, st, p);
-    else
-        hipLaunchKernelGGL(k_cert_finalize, dim3(blocks_for((uint64_t)p.ncerts * 64, 256)), dim3(256), 0, st, p);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
+    if (e != hipSuccess || t.exact_grid == 0) return e;
     // the exact list's length is on the device: a capped grid that exits at once when it is empty
-    hipLaunchKernelGGL(k_cert_exact, dim3(std::min<uint32_t>(p.ncerts, EXACT_MAX_BLOCKS)), dim3(64), 0, st, p);
+    hipLaunchKernelGGL(k_cert_exact, dim3(t.exact_grid), dim3(64), 0, st, p);
     return hipGetLastError();
 }
 
-hipError_t launch_prep_expand(uint32_t ncerts, uint32_t nsigs, uint32_t nkeys, const uint32_t* first,
-                              const uint32_t* nv, const uint32_t* signer, uint32_t* sig_cert, uint32_t* zero4,
-                              uint32_t* counts, uint32_t* status, uint32_t* cert_state, hipStream_t st) {
-    const uint32_t prep_blocks = std::min<uint32_t>(blocks_for(std::max(nsigs + 1, ncerts), 256), 1024u);
-    hipLaunchKernelGGL(k_prep_certs, dim3(prep_blocks), dim3(256), 0, st, nsigs, nkeys, sig_cert, counts, zero4, status,
+hipError_t launch_prep_expand(const PreamblePlan& pl, uint32_t ncerts, uint32_t nsigs, uint32_t nkeys,
+                              const uint32_t* first, const uint32_t* nv, const uint32_t* signer, uint32_t* sig_cert,
+                              uint32_t* zero4, uint32_t* counts, uint32_t* status, uint32_t* cert_state, hipStream_t st) {
+    hipLaunchKernelGGL(k_prep_certs, dim3(pl.prep_grid), dim3(256), 0, st, nsigs, nkeys, sig_cert, counts, zero4, status,
                        ncerts, cert_state);
-    const bool tiles = (counts || status) && nsigs > 0;
-    // waves per certificate from the average vote count (a performance choice only)
-    const uint64_t avg_votes = ncerts ? nsigs / ncerts : 0;
-    const uint32_t wlog = avg_votes > 512 ? 2u : (avg_votes > 128 ? 1u : 0u);
-    const uint32_t nb = std::max<uint32_t>(blocks_for(ncerts, EXPAND_WAVES_PER_BLOCK >> wlog),
-                                           tiles ? blocks_for(nsigs, GROUP_TILE) : 0u);
-    if (nb == 0) return hipGetLastError();
-    const size_t lds = counts && nkeys <= GROUP_LDS_KEYS ? (size_t)nkeys * 4 : 0;
-    hipLaunchKernelGGL(k_expand_count, dim3(nb), dim3(256), lds, st, ncerts, nsigs, nkeys, first, nv, signer, sig_cert,
-                       counts, status, cert_state, wlog);
+    if (pl.expand_grid == 0) return hipGetLastError();
+    hipLaunchKernelGGL(k_expand_count, dim3(pl.expand_grid), dim3(256), pl.expand_lds, st, ncerts, nsigs, nkeys, first,
+                       nv, signer, sig_cert, counts, status, cert_state, pl.expand_wlog);
     return hipGetLastError();
 }
 
 // Scan + scatter of the signer grouping whose counts k_expand_count produced.
-hipError_t launch_group_scatter(uint32_t n, uint32_t nkeys, const uint32_t* signer, const uint32_t* sig_cert,
-                                const uint32_t* counts, uint32_t* cursor, uint32_t* perm, uint2* pinfo,
-                                hipStream_t st) {
-    if (n == 0 || nkeys == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_scan_slots, dim3(1), dim3(1024), 0, st, nkeys, counts, cursor);
-    if (nkeys <= GROUP_LDS_KEYS)
-        hipLaunchKernelGGL(k_scatter_slots_lds, dim3(blocks_for(n, GROUP_TILE)), dim3(256), nkeys * 8, st, n, nkeys,
-                           signer, sig_cert, cursor, perm, pinfo);
+hipError_t launch_group_scatter(const GroupPlan& g, uint32_t n, uint32_t nkeys, const uint32_t* signer,
+                                const uint32_t* sig_cert, const uint32_t* counts, uint32_t* cursor, uint32_t* perm,
+                                uint2* pinfo, hipStream_t st) {
+    hipLaunchKernelGGL(k_scan_slots, dim3(g.scan_grid), dim3(1024), 0, st, nkeys, counts, cursor);
+    if (g.form == GroupPlan::LDS)
+        hipLaunchKernelGGL(k_scatter_slots_lds, dim3(g.scatter_grid), dim3(256), g.scatter_lds, st, n, nkeys, signer,
+                           sig_cert, cursor, perm, pinfo);
     else
-        hipLaunchKernelGGL(k_scatter_slots, dim3(blocks_for(n, 256)), dim3(256), 0, st, n, nkeys, signer, sig_cert,
-                           cursor, perm, pinfo);
+        hipLaunchKernelGGL(k_scatter_slots, dim3(g.scatter_grid), dim3(256), 0, st, n, nkeys, signer, sig_cert, cursor,
+                           perm, pinfo);
     return hipGetLastError();
 }
 

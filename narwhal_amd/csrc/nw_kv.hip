@@ -8,5 +8,5 @@
 
 namespace nw {
 template hipError_t launch_vs_wa<NW_WA>(const VerifyParams&, int, bool, uint32_t, hipStream_t);
-template hipError_t launch_slow_tail_wa<NW_WA>(const VerifyParams&, const FinalizeParams&, int, hipStream_t);
+template hipError_t launch_slow_tail_wa<NW_WA>(const VerifyParams&, const FinalizeParams&, int, uint32_t, hipStream_t);
 }  // namespace nw

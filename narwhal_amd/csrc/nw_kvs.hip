@@ -7,5 +7,5 @@
 #endif
 
 namespace nw {
-template hipError_t launch_split_wa<NW_WA>(const VerifyParams&, int, hipStream_t);
+template hipError_t launch_split_wa<NW_WA>(const VerifyParams&, int, bool, uint32_t, hipStream_t);
 }  // namespace nw

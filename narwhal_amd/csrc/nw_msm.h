@@ -65,7 +65,11 @@ struct MsmParams {
 hipError_t launch_msm(const MsmParams& p, hipStream_t st);
 hipError_t launch_msm_points_identity(uint32_t npts, const uint32_t* pts, uint8_t* out, hipStream_t st);
 // Strict verify of uncached keys: VerifyParams.sig_keys holds each signature's raw key words.
+// Up to VAR_QUAD_MAX_SIGS signatures the quad form (a quad per signature, one-wave blocks of 16),
+// above it the lane form; which, and the grid, is the host plan's (nw_host_plan.h: VarPlan).
+static constexpr uint32_t VAR_QUAD_MAX_SIGS = 4096;
 struct VerifyParams;
-hipError_t launch_verify_var(const VerifyParams& p, int msgmode, uint32_t* scratch, hipStream_t st);
+hipError_t launch_verify_var(const VerifyParams& p, int msgmode, bool quad, uint32_t grid, uint32_t* scratch,
+                             hipStream_t st);
 
 }  // namespace nw

@@ -201,7 +201,7 @@ __device__ ge_p3 ge_scalarmult_w4_quad(const uint32_t k_in[8], const ge_p3& Q, u
 // QUAD (at most VAR_QUAD_MAX_SIGS signatures: one-wave blocks of 16 quads, at most one wave per
 // SIMD of the chip): a quad per signature and ge_scalarmult_w4_quad; quads past gn run duplicates
 // (full EXEC) and store nothing.  Above that the lane-per-signature kernel has the throughput.
-static constexpr uint32_t VAR_QUAD_MAX_SIGS = 4096;
+static_assert(VAR_QUAD_MAX_SIGS / 16 <= 256 * 4, "quad form: at most one one-wave block per SIMD");
 template <bool QUAD>
 __global__ void __launch_bounds__(QUAD ? 64 : 256) k_verify_var(VerifyParams a, uint32_t* scratch) {
     __shared__ uint32_t qtab[QUAD ? 16 * 320 : 1];
@@ -606,12 +606,11 @@ hipError_t launch_msm_points_identity(uint32_t npts, const uint32_t* pts, uint8_
     return hipGetLastError();
 }
 
-hipError_t launch_verify_var(const VerifyParams& p, int msgmode, uint32_t* scratch, hipStream_t st) {
-    if (p.gn == 0) return hipSuccess;
+hipError_t launch_verify_var(const VerifyParams& p, int msgmode, bool quad, uint32_t grid, uint32_t* scratch,
+                             hipStream_t st) {
     if (msgmode != 1) return hipErrorInvalidValue;
-    if (p.gn <= VAR_QUAD_MAX_SIGS)
-        hipLaunchKernelGGL(k_verify_var<true>, dim3((p.gn + 15) / 16), dim3(64), 0, st, p, scratch);
-    else hipLaunchKernelGGL(k_verify_var<false>, dim3(blocks_for(p.gn, 256)), dim3(256), 0, st, p, scratch);
+    if (quad) hipLaunchKernelGGL(k_verify_var<true>, dim3(grid), dim3(64), 0, st, p, scratch);
+    else hipLaunchKernelGGL(k_verify_var<false>, dim3(grid), dim3(256), 0, st, p, scratch);
     return hipGetLastError();
 }
 #endif  // NW_MSM_PART

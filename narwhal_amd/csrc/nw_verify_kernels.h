@@ -128,10 +128,10 @@ __global__ void __launch_bounds__(256, MSGMODE == 0 ? NW_VERIFY_WAVES : 1) k_ver
     store_prec_soa(a.pbuf, a.n, gid, P, park_mismatch<false>(a, i2, P, verify_pflags(P, R, frow[gid])));
 }
 
-// Latency-mode kernel for small launches (nw_verify_split.h, compiled in nw_kvs.hip).
-static constexpr uint32_t VERIFY_SPLIT_MAX_SIGS = 16384;
+// Latency-mode kernel for launches of up to VERIFY_SPLIT_MAX_SIGS (nw_verify_split.h, compiled in
+// nw_kvs.hip); fuse: k_finish's work done in the kernel (launches of up to SPLIT_FUSE_MAX_SIGS).
 template <int WA>
-hipError_t launch_split_wa(const VerifyParams& p, int msgmode, hipStream_t st);
+hipError_t launch_split_wa(const VerifyParams& p, int msgmode, bool fuse, uint32_t grid, hipStream_t st);
 
 // Exact path, step 1 (one lane per entry of the slow list, grid-stride): for a signature whose
 // strict equation fails in a certificate not yet rejected, decode R (failure: F_R_BAD, and the
@@ -225,7 +225,7 @@ __global__ void __launch_bounds__(256) k_slow_prep(VerifyParams a) {
 // 256-thread workgroups (64 quads) with the entries dealt to the blocks first: an adversarial
 // batch's few hundred entries land on wave 0 of every block, one working wave per CU (one-wave
 // blocks were packed up to three to a SIMD by the dispatcher, stretching the serial chains).
-static constexpr uint32_t SLOW_MUL_QUADS = 64;   // per 256-thread workgroup
+static_assert(SLOW_MUL_QUADS * 4 == 256, "k_slow_mul: a quad per entry, 256-thread workgroups");
 __device__ __forceinline__ void slow_mul(const VerifyParams& a, uint32_t bid, uint32_t nb, uint32_t (*tab)[8][40]) {
     const uint32_t cnt = *a.slow_count;
     const uint32_t qd = threadIdx.x >> 2, q = threadIdx.x & 3u;
@@ -309,17 +309,12 @@ __global__ void __launch_bounds__(256) k_slow_tail(VerifyParams a, FinalizeParam
     cert_tail(f, threadIdx.x, reinterpret_cast<uint32_t (*)[40]>(&tab[0][0][0]));
 }
 
-// Launch k_verify (slow = false, grid over p.gn) or k_slow_prep (slow = true: a grid-stride grid
-// capped at one 256-thread block per CU, so an honest batch's empty exact path costs one small
-// dispatch whatever n_upper is).
-static constexpr uint32_t SLOW_MAX_BLOCKS = 256;
+// Launch k_verify (slow = false: a lane per signature) or k_slow_prep (slow = true: a grid-stride
+// grid capped at SLOW_MAX_BLOCKS, one 256-thread block per CU, so an honest batch's empty exact path
+// costs one small dispatch whatever the batch size) over the grid the host plan gives.
 template <int WA>
-hipError_t launch_vs_wa(const VerifyParams& p, int msgmode, bool slow, uint32_t n_upper, hipStream_t st) {
-    const dim3 b(256);
-    uint32_t nb = blocks_for(slow ? n_upper : p.gn, 256);
-    if (slow && nb > SLOW_MAX_BLOCKS) nb = SLOW_MAX_BLOCKS;
-    const dim3 g(nb);
-    if (!slow && p.gn <= VERIFY_SPLIT_MAX_SIGS) return launch_split_wa<WA>(p, msgmode, st);
+hipError_t launch_vs_wa(const VerifyParams& p, int msgmode, bool slow, uint32_t grid, hipStream_t st) {
+    const dim3 b(256), g(grid);
     if (msgmode == 0) {
         if (slow) hipLaunchKernelGGL((k_slow_prep<0, WA>), g, b, 0, st, p);
         else if (p.key_negtab) hipLaunchKernelGGL((k_verify<0, WA, true>), g, b, 0, st, p);
@@ -333,10 +328,11 @@ hipError_t launch_vs_wa(const VerifyParams& p, int msgmode, bool slow, uint32_t 
 }
 
 template <int WA>
-hipError_t launch_slow_tail_wa(const VerifyParams& p, const FinalizeParams& f, int msgmode, hipStream_t st) {
-    if (!slow_tail_fits(f.ncerts, f.nsigs)) return hipErrorInvalidValue;
-    if (msgmode == 0) hipLaunchKernelGGL((k_slow_tail<0, WA>), dim3(1), dim3(256), 0, st, p, f);
-    else hipLaunchKernelGGL((k_slow_tail<1, WA>), dim3(1), dim3(256), 0, st, p, f);
+hipError_t launch_slow_tail_wa(const VerifyParams& p, const FinalizeParams& f, int msgmode, uint32_t grid,
+                               hipStream_t st) {
+    if (grid != 1) return hipErrorInvalidValue;   // one workgroup runs all three phases
+    if (msgmode == 0) hipLaunchKernelGGL((k_slow_tail<0, WA>), dim3(grid), dim3(256), 0, st, p, f);
+    else hipLaunchKernelGGL((k_slow_tail<1, WA>), dim3(grid), dim3(256), 0, st, p, f);
     return hipGetLastError();
 }
 

@@ -17,8 +17,8 @@ namespace nw {
 // 8 lanes per signature: ceil(NPOS / 8) mixed additions per lane (3 at W20) + 3 shuffle levels of
 // full additions = 6 dependent point operations (~51 field products) against 6 + 2 (~62) with 4
 // lanes; 16 lanes would be 2 + 4 (~54).
-static constexpr int VERIFY_SPLIT = 8;
-// VERIFY_SPLIT_MAX_SIGS (nw_verify_kernels.h): the split grid is then <= two waves per SIMD
+// (VERIFY_SPLIT = 8, nw_kernels.h)
+// VERIFY_SPLIT_MAX_SIGS (nw_kernels.h): the split grid is then <= two waves per SIMD
 // (1,024 SIMDs x 64 lanes x 2 / VERIFY_SPLIT)
 static_assert(VERIFY_SPLIT_MAX_SIGS * VERIFY_SPLIT <= 2 * 256 * 4 * 64, "split grid larger than two waves per SIMD");
 static_assert(SPLIT_FUSE_MAX_SIGS <= VERIFY_SPLIT_MAX_SIGS, "a fused launch must take the split kernel");
@@ -53,7 +53,7 @@ NW_HD int low_digit(const uint32_t kp[9]) {
     return (int)(kp[0] & ((1u << W) - 1u)) - (1 << (W - 1));
 }
 
-// FUSE (split_fuses_finish: launches of up to SPLIT_FUSE_MAX_SIGS signatures, one per k_finish lane):
+// FUSE (CertPlan: launches of up to SPLIT_FUSE_MAX_SIGS signatures, one per k_finish lane):
 // after the butterfly every lane of a group holds P, so all 8 lanes run k_finish's work for their
 // signature (the inversion on a dense EXEC mask) and the group's first lane writes the verdict:
 // no k_finish launch and no P round trip through pbuf (a single header / vote check: ~5 us).
@@ -159,9 +159,8 @@ __global__ void __launch_bounds__(256) k_verify_split(VerifyParams a) {
 }
 
 template <int WA>
-hipError_t launch_split_wa(const VerifyParams& p, int msgmode, hipStream_t st) {
-    const dim3 b(256), g(blocks_for((uint64_t)p.gn * VERIFY_SPLIT, 256));
-    const bool fuse = split_fuses_finish(p.gn, p.fk);
+hipError_t launch_split_wa(const VerifyParams& p, int msgmode, bool fuse, uint32_t grid, hipStream_t st) {
+    const dim3 b(256), g(grid);
     if (msgmode == 0) {
         if (fuse) hipLaunchKernelGGL((k_verify_split<0, WA, true>), g, b, 0, st, p);
         else hipLaunchKernelGGL((k_verify_split<0, WA, false>), g, b, 0, st, p);

@@ -119,6 +119,59 @@ static void check_digest(const std::vector<size_t>& len) {
             if (len[i]) h[l.data + p.off[i] + len[i] - 1] = 1;
 }
 
+// The launch plan over every switch of its ladders: the scratch has the grouping segments exactly
+// where the plan groups, launches() counts the stages with a grid, a stage's form and grid agree.
+static void check_plan(size_t ncerts, size_t nsigs, size_t nkeys, uint32_t batch_mode, bool prestaged, bool status,
+                       uint32_t fk) {
+    const CertPlan p(ncerts, nsigs, nkeys, batch_mode, prestaged, status, fk);
+    const CertScratch s(p, true);
+    CHECK(s.group == p.groups() && (s.perm != s.pinfo) == p.groups());
+    CHECK(p.groups() == (p.group.scan_grid == 1) && p.groups() == (p.group.scatter_grid != 0));
+    CHECK(!p.groups() || p.preamble.expand_grid >= (nsigs + GROUP_TILE - 1) / GROUP_TILE);
+    CHECK(prestaged == (p.preamble.prep_grid == 0) && (p.preamble.prep_grid || !p.preamble.expand_grid));
+    CHECK((p.verify.form == VerifyPlan::SKIP) == (nsigs == 0) && (p.verify.grid == 0) == (nsigs == 0));
+    CHECK((p.finish.form == FinishPlan::NONE) == (p.finish.grid == 0));
+    CHECK((p.verify.form == VerifyPlan::SPLIT_FUSED) == (nsigs > 0 && p.finish.form == FinishPlan::NONE));
+    CHECK(p.finish.fk >= 1 && (p.finish.form == FinishPlan::ONE) == (p.finish.grid != 0 && p.finish.fk == 1));
+    CHECK((p.tail.form == TailPlan::NONE) == (batch_mode == 0));
+    CHECK((p.tail.form == TailPlan::SLOW_TAIL) == (p.tail.slow_tail_grid == 1));
+    CHECK((p.tail.finalize == TailPlan::F_NONE) == (p.tail.finalize_grid == 0));
+    CHECK(p.tail.slow_prep_grid <= SLOW_MAX_BLOCKS && p.tail.slow_mul_grid <= SLOW_MAX_BLOCKS &&
+          p.tail.exact_grid <= EXACT_MAX_BLOCKS);
+    const uint32_t stages = (p.preamble.prep_grid != 0) + (p.preamble.expand_grid != 0) + 2 * p.groups() +
+                            (p.verify.form != VerifyPlan::SKIP) + (p.finish.form != FinishPlan::NONE) +
+                            (p.tail.form == TailPlan::SLOW_TAIL) + (p.tail.slow_prep_grid != 0) +
+                            (p.tail.slow_mul_grid != 0) + (p.tail.finalize != TailPlan::F_NONE) +
+                            (p.tail.exact_grid != 0);
+    CHECK(p.launches() == stages);
+}
+
+static void check_plans() {
+    const size_t sigs[] = {0, 1, 63, 64, 255, 256, 257, 4096, 4097, 16383, 16384, 16385, 65536, 65537,
+                           262144 * 2, 262144 * 2 + 1, 262144 * 16, 262144 * 16 + 1, 0xFFFFFFF0u};
+    for (size_t nsigs : sigs)
+        for (size_t ncerts : {(size_t)0, (size_t)1, (size_t)16, (size_t)17, nsigs / 129 + 1, nsigs / 1025 + 1, (size_t)0xFFFFFFF0u})
+            for (size_t nkeys : {(size_t)0, (size_t)1, (size_t)2, (size_t)8192, (size_t)8193})
+                for (uint32_t batch_mode : {0u, 1u})
+                    for (bool prestaged : {false, true})
+                        for (uint32_t fk : {0u, 1u, 16u}) {
+                            check_plan(ncerts, nsigs, nkeys, batch_mode, prestaged, false, fk);
+                            check_plan(ncerts, nsigs, nkeys, batch_mode, prestaged, true, fk);
+                        }
+    // the shapes DESIGN.md's table names
+    const CertPlan one(1, 1, 4, 0, true, false, 0), cert(1, 67, 4, 1, true, false, 0);
+    CHECK(one.launches() == 1 && one.verify.form == VerifyPlan::SPLIT_FUSED && one.verify.grid == 1);
+    CHECK(cert.launches() == 2 && cert.tail.form == TailPlan::SLOW_TAIL);
+    const CertPlan c2(14926, 14926 * 67, 100, 1, false, false, 0);
+    CHECK(c2.launches() == 10 && c2.group.form == GroupPlan::LDS && c2.verify.form == VerifyPlan::FULL &&
+          c2.finish.form == FinishPlan::CHUNKED && c2.finish.fk == 4 && c2.tail.finalize == TailPlan::WAVE);
+    for (size_t n : {(size_t)0, (size_t)1, (size_t)4096, (size_t)4097, (size_t)65536, (size_t)65537, (size_t)0xFFFFFFF0u}) {
+        const VarPlan v(n, 0);
+        CHECK(v.quad == (n <= 4096) && v.grid == (n + (v.quad ? 15 : 255)) / (v.quad ? 16 : 256));
+        CHECK(v.launches() == (n ? 2u : 0u) && (v.finish.form == FinishPlan::ONE) == (n >= 1 && n <= 65536));
+    }
+}
+
 int main() {
     const uint32_t top = 0xFFFFFFFFu;
     {
@@ -151,6 +204,7 @@ int main() {
         const CoreScratch cs2(l2, 3, 1, 67, 4);
         CHECK(!cs2.strict.group && !cs2.certs.group && cs2.bytes() == cs2.certs.bytes());
     }
+    check_plans();
     const size_t M4 = (size_t)4 << 20;
     check_digest({});
     check_digest({0, 0});

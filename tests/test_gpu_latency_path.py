@@ -4,7 +4,8 @@ wrong sign, bad S, ...):
 
   <= 16,384 signatures   k_verify_split (8 lanes per signature) + k_finish<true> (one inversion per lane;
                          variable-time for <= 8 signatures)
-  > 16,384               k_verify + k_finish
+  > 16,384               k_verify + k_finish (one signature per lane, k_finish<true>, up to 65,536;
+                         the chunked k_finish<false> from 65,537)
 
 Each must reproduce the oracle's verify_strict verdict (tests/golden adversarial_strict) bit for bit.
 """
@@ -42,7 +43,7 @@ def test_each_case_alone(adv):
         assert ok == [c["strict"]], c["name"]
 
 
-@pytest.mark.parametrize("target", [8, 9, 67, 2048, 16384, 16385, 20000])
+@pytest.mark.parametrize("target", [8, 9, 67, 2048, 16384, 16385, 20000, 65536, 65537])
 def test_launch_sizes(adv, target):
     eng, cases, slots = adv
     got = _run(eng, cases, slots, target)

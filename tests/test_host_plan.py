@@ -1,6 +1,6 @@
 """CPU: the host planning of the C-ABI layer (narwhal_amd/csrc/nw_host_plan.h): range validation, the
 preamble state of small calls, the staging layouts, the MSM task plan, the asynchronous digest's
-chunking, the committee window and the k_finish lane depth.  The header is compiled for the host
+chunking, the committee window, the k_finish lane depth and the launch plan.  The header is compiled for the host
 into a small shim (as tests/test_host_scalar.py does) and every expected value is restated here in
 Python.  The same header also runs under AddressSanitizer + UBSan as a stand-alone program
 (tests/host_plan_check.cpp); nothing sanitized is loaded into Python.
@@ -120,6 +120,25 @@ int t_committee_window(size_t n, double headroom, size_t budget) {
 }
 uint32_t t_finish_k_for(uint32_t fixed, size_t n) { return finish_k_for(fixed, n); }
 int t_finish_k_max() { return FINISH_K; }
+// every field of the launch plan (PLAN_FIELDS below), then launches(); returns whether the scratch made
+// from the plan has the grouping segments
+int t_cert_plan(size_t ncerts, size_t nsigs, size_t nkeys, uint32_t batch_mode, int prestaged, int status, uint32_t fk,
+                uint32_t* o) {
+    const CertPlan p(ncerts, nsigs, nkeys, batch_mode, prestaged != 0, status != 0, fk);
+    const uint32_t f[] = {p.preamble.prep_grid, p.preamble.expand_grid, p.preamble.expand_wlog, p.preamble.expand_lds,
+                          p.group.form, p.group.scan_grid, p.group.scatter_grid, p.group.scatter_lds,
+                          p.verify.form, p.verify.grid, p.finish.form, p.finish.fk, p.finish.grid,
+                          p.tail.form, p.tail.slow_tail_grid, p.tail.slow_prep_grid, p.tail.slow_mul_grid,
+                          p.tail.finalize, p.tail.finalize_grid, p.tail.exact_grid, p.launches()};
+    std::memcpy(o, f, sizeof f);
+    const CertScratch s(p, true);
+    return (s.cursor > s.counts && s.perm > s.cursor && s.pinfo > s.perm && s.bytes() > s.pinfo) ? 1 : 0;
+}
+void t_var_plan(size_t n, uint32_t fk, uint32_t* o) {
+    const VarPlan p(n, fk);
+    const uint32_t f[] = {p.quad, p.grid, p.finish.form, p.finish.fk, p.finish.grid, p.launches()};
+    std::memcpy(o, f, sizeof f);
+}
 }
 """
 
@@ -561,6 +580,213 @@ def test_finish_k_for_table(lib):
         for fixed in (0, 1, 5, 16):
             assert lib.t_finish_k_for(fixed, n) == want(fixed, n), (fixed, n)
     assert [lib.t_finish_k_for(0, n) for n in (65536, 65537, 262144 * 16 + 1)] == [1, 2, 16]
+
+
+# ---------------------------------------------------------------- launch plan
+# What a run of the certificate pipeline launches, restated from the launchers as they stood before
+# the plan existed (the ``if`` ladders of launch_prep_expand, launch_group_scatter, launch_verify /
+# launch_vs_wa / launch_split_wa, launch_finish, launch_slow, launch_finalize and enqueue_certs), one
+# function per launcher, each returning what it would have launched.
+
+PLAN_FIELDS = ["prep_grid", "expand_grid", "expand_wlog", "expand_lds", "group", "scan_grid", "scatter_grid",
+               "scatter_lds", "verify", "verify_grid", "finish", "fk", "finish_grid", "tail", "slow_tail_grid",
+               "slow_prep_grid", "slow_mul_grid", "finalize", "finalize_grid", "exact_grid", "launches"]
+G_OFF, G_LDS, G_GLOBAL = 0, 1, 2
+V_SKIP, V_SPLIT_FUSED, V_SPLIT, V_FULL = 0, 1, 2, 3
+FIN_NONE, FIN_ONE, FIN_CHUNKED = 0, 1, 2
+T_NONE, T_SLOW_TAIL, T_GRID = 0, 1, 2
+F_NONE, F_CERT_TAIL, F_WAVE, F_WG256, F_WG1024 = 0, 1, 2, 3, 4
+
+
+def _blocks(n, t):
+    return -(-n // t)
+
+
+def _old_finish_k_for(fixed, n):
+    if fixed:
+        return fixed
+    if n <= 65536:
+        return 1
+    return min(max(_blocks(n, 262144), 2), 16)
+
+
+def _old_prep_expand(ncerts, nsigs, nkeys, counts, status):
+    prep = min(_blocks(max(nsigs + 1, ncerts), 256), 1024)
+    tiles = (counts or status) and nsigs > 0
+    avg = nsigs // ncerts if ncerts else 0
+    wlog = 2 if avg > 512 else (1 if avg > 128 else 0)
+    nb = max(_blocks(ncerts, 4 >> wlog), _blocks(nsigs, 4096) if tiles else 0)
+    lds = nkeys * 4 if counts and nkeys <= 8192 else 0
+    return dict(prep_grid=prep, expand_grid=nb, expand_wlog=wlog, expand_lds=lds if nb else 0)
+
+
+def _old_group_scatter(n, nkeys):
+    if n == 0 or nkeys == 0:
+        return {}
+    if nkeys <= 8192:
+        return dict(group=G_LDS, scan_grid=1, scatter_grid=_blocks(n, 4096), scatter_lds=nkeys * 8)
+    return dict(group=G_GLOBAL, scan_grid=1, scatter_grid=_blocks(n, 256), scatter_lds=0)
+
+
+def _old_verify(gn, fk):
+    if gn == 0:
+        return {}
+    if gn <= 16384:
+        fuse = gn <= 4096 and fk == 1
+        return dict(verify=V_SPLIT_FUSED if fuse else V_SPLIT, verify_grid=_blocks(gn * 8, 256))
+    return dict(verify=V_FULL, verify_grid=_blocks(gn, 256))
+
+
+def _old_finish(gn, fk):
+    if gn == 0:
+        return {}
+    lanes = _blocks(gn, fk)
+    return dict(finish=FIN_ONE if fk == 1 else FIN_CHUNKED, finish_grid=_blocks(lanes, 256))
+
+
+def _old_slow(n_upper):
+    if n_upper == 0:
+        return {}
+    return dict(slow_prep_grid=min(_blocks(n_upper, 256), 256), slow_mul_grid=min(_blocks(n_upper, 64), 256))
+
+
+def _old_finalize(ncerts, nsigs):
+    if ncerts == 0:
+        return {}
+    if ncerts <= 16 and nsigs <= 64 * 1024:
+        return dict(finalize=F_CERT_TAIL, finalize_grid=1)
+    avg = nsigs // ncerts
+    if avg > 1024:
+        r = dict(finalize=F_WG1024, finalize_grid=ncerts)
+    elif avg > 256:
+        r = dict(finalize=F_WG256, finalize_grid=ncerts)
+    else:
+        r = dict(finalize=F_WAVE, finalize_grid=_blocks(ncerts * 64, 256))
+    r["exact_grid"] = min(ncerts, 1024)
+    return r
+
+
+def _old_enqueue_certs(ncerts, nsigs, nkeys, batch_mode, prestaged, status, pinned_fk):
+    """The launches of one run, in the parent's order; a stage that is not launched keeps grid 0."""
+    w = dict.fromkeys(PLAN_FIELDS, 0)
+    group = (not prestaged) and nsigs >= 16384 and nkeys > 1 and nsigs >= 4 * nkeys     # groups_signers
+    if not prestaged:
+        w.update(_old_prep_expand(ncerts, nsigs, nkeys, group, status))
+    if group:
+        w.update(_old_group_scatter(nsigs, nkeys))
+    w["fk"] = _old_finish_k_for(pinned_fk, nsigs)
+    w.update(_old_verify(nsigs, w["fk"]))
+    if not (nsigs <= 4096 and w["fk"] == 1):                                           # split_fuses_finish
+        w.update(_old_finish(nsigs, w["fk"]))
+    if batch_mode:
+        if 1 <= ncerts <= 16 and 1 <= nsigs <= 256:                                    # slow_tail_fits
+            w.update(tail=T_SLOW_TAIL, slow_tail_grid=1)
+        else:
+            w["tail"] = T_GRID
+            w.update(_old_slow(nsigs))
+            w.update(_old_finalize(ncerts, nsigs))
+    grids = [k for k in PLAN_FIELDS if k.endswith("grid")]
+    w["launches"] = sum(1 for k in grids if w[k])
+    return w, group
+
+
+def _plan(lib, ncerts, nsigs, nkeys, batch_mode, prestaged, status, fk):
+    o = (ctypes.c_uint32 * len(PLAN_FIELDS))()
+    has_group_segments = lib.t_cert_plan(_sz(ncerts), _sz(nsigs), _sz(nkeys), batch_mode, int(prestaged), int(status),
+                                         fk, o)
+    return dict(zip(PLAN_FIELDS, o)), bool(has_group_segments)
+
+
+PLAN_NSIGS = [0, 1, 63, 64, 255, 256, 257, 4096, 4097, 16383, 16384, 16385, 65536, 65537, 262144 * 2, 262144 * 2 + 1,
+              262144 * 16, 262144 * 16 + 1]
+
+
+def _plan_ncerts(nsigs):
+    """0 | 1 | 16 | 17, and certificate counts that put the average votes on either side of every switch."""
+    out = {0, 1, 16, 17}
+    for avg in (128, 256, 512, 1024):
+        for a in (avg, avg + 1):
+            c = nsigs // a                       # the largest count whose average is still >= a ...
+            if c and nsigs // c == a:
+                out.add(c)
+            c = nsigs // (a + 1) + 1             # ... and the smallest whose average is <= a
+            if nsigs // c == a:
+                out.add(c)
+    return sorted(out)
+
+
+def _plan_nkeys(nsigs):
+    """0 | 1 | 2 | 8192 | 8193, and key counts with nsigs >= 4 nkeys on both sides."""
+    return sorted({0, 1, 2, 8192, 8193, nsigs // 4, nsigs // 4 + 1})
+
+
+@pytest.mark.parametrize("nsigs", PLAN_NSIGS)
+def test_cert_plan_equals_the_launchers_ladders(lib, nsigs):
+    seen = set()
+    for ncerts in _plan_ncerts(nsigs):
+        for nkeys in _plan_nkeys(nsigs):
+            for batch_mode in (0, 1):
+                for prestaged in (False, True):
+                    for status in (False, True):
+                        for fk in (0, 1, 16):
+                            args = (ncerts, nsigs, nkeys, batch_mode, prestaged, status, fk)
+                            got, has_group_segments = _plan(lib, *args)
+                            want, group = _old_enqueue_certs(*args)
+                            assert got == want, (args, {k: (got[k], want[k]) for k in got if got[k] != want[k]})
+                            # the plan groups only where the scratch has the grouping segments
+                            assert (got["group"] != G_OFF) == group == has_group_segments, args
+                            # launches() is the number of stages that are not skipped
+                            stages = [got["prep_grid"] != 0, got["expand_grid"] != 0, got["group"] != G_OFF,
+                                      got["group"] != G_OFF, got["verify"] != V_SKIP, got["finish"] != FIN_NONE,
+                                      got["tail"] == T_SLOW_TAIL, got["slow_prep_grid"] != 0, got["slow_mul_grid"] != 0,
+                                      got["finalize"] != F_NONE, got["exact_grid"] != 0]
+                            assert got["launches"] == sum(stages), args
+                            seen.add((got["group"], got["verify"], got["finish"], got["tail"], got["finalize"]))
+    # every form the size can take was reached
+    forms = lambda i: {s[i] for s in seen}
+    assert forms(1) == ({V_SKIP} if nsigs == 0 else {V_SPLIT_FUSED, V_SPLIT} if nsigs <= 4096
+                        else {V_SPLIT} if nsigs <= 16384 else {V_FULL})
+    assert forms(0) == ({G_OFF} if nsigs < 16384 else {G_OFF, G_LDS, G_GLOBAL} if nsigs >= 4 * 8193 else {G_OFF, G_LDS})
+    assert forms(3) == ({T_NONE, T_SLOW_TAIL, T_GRID} if 1 <= nsigs <= 256 else {T_NONE, T_GRID})
+
+
+def test_cert_plan_average_vote_switches(lib):
+    """Both sides of 128 | 129, 512 | 513 (k_expand_count's waves per certificate) and of 256 | 257,
+    1024 | 1025 (the finalize form), with exact certificate counts."""
+    ncerts = 100
+    for avg, field, below, above in ((128, "expand_wlog", 0, 1), (512, "expand_wlog", 1, 2),
+                                     (256, "finalize", F_WAVE, F_WG256), (1024, "finalize", F_WG256, F_WG1024)):
+        for a, want in ((avg, below), (avg + 1, above)):
+            got, _ = _plan(lib, ncerts, ncerts * a, 4, 1, False, False, 0)
+            assert got[field] == want, (a, field)
+            assert got == _old_enqueue_certs(ncerts, ncerts * a, 4, 1, False, False, 0)[0]
+
+
+def test_cert_plan_named_shapes(lib):
+    """The launch counts DESIGN.md quotes."""
+    def launches(*a):
+        return _plan(lib, *a)[0]["launches"]
+    assert launches(1, 1, 4, 0, True, False, 0) == 1               # one strict signature: k_verify_split<FUSE>
+    assert launches(1, 67, 4, 1, True, False, 0) == 2              # one certificate: + k_slow_tail
+    assert launches(16, 256, 4, 1, True, False, 0) == 2
+    assert launches(17, 272, 4, 1, True, False, 0) == 5            # + k_slow_prep, k_slow_mul, k_cert_finalize, k_cert_exact
+    assert launches(1, 4097, 4, 1, True, False, 0) == 5            # k_finish<ONE>, the slow pair, k_cert_tail
+    assert launches(14926, 14926 * 67, 100, 1, False, False, 0) == 10   # C2
+
+
+def test_var_plan(lib):
+    """k_verify_var: the quad form (16 signatures per one-wave block) up to 4,096 signatures, the lane form
+    above; then k_finish, never fused."""
+    for n in (0, 1, 16, 17, 4096, 4097, 65536, 65537, 262144 * 2 + 1, 262144 * 16 + 1):
+        for fk in (0, 1, 16):
+            o = (ctypes.c_uint32 * 6)()
+            lib.t_var_plan(_sz(n), fk, o)
+            k = _old_finish_k_for(fk, n)
+            fin = _old_finish(n, k)
+            quad = n <= 4096
+            want = [int(quad), _blocks(n, 16) if quad else _blocks(n, 256), fin.get("finish", FIN_NONE), k,
+                    fin.get("finish_grid", 0), 2 if n else 0]
+            assert list(o) == want, (n, fk)
 
 
 # ---------------------------------------------------------------- sanitizer run (stand-alone program)
