@@ -7,11 +7,18 @@
 // give the scheduler ILP; the carry chain interleaves two halves (0..4 / 5..9).
 //
 // Limb-size discipline ("k" = limbs <= k * 2^26 even / k * 2^25 odd):
-//   * tight (k ~ 1): output of fe_mul / fe_sq / fe_sub / fe_carry / fe_frombytes
+//   * tight (k ~ 1): output of fe_mul / fe_sq / fe_sub / fe_carry / fe_frombytes.  Limb by limb: every
+//     limb <= its mask, except limb 1 <= 2^25 + 2^18 (the x19 wrap carry lands there), limb 5 <=
+//     2^25 + 2^13 (fe_reduce_wide's second carry out of limb 4) and limb 6 <= 2^26 (fe_carry's last
+//     carry out of limb 5).  Sums and differences of tight values inherit these excesses.
 //   * fe_add of two tight values: k = 2;  one more add: k = 3
 //   * fe_mul(h, f, g) requires k_g <= 3 (19*g must fit 32 bits) and k_f * k_g <= 32
 //     (u64 column sums stay below 2^64); every call site below respects k <= 3.
-//   * fe_sub(h, f, g) requires k_g <= 3 (uses f + 4p - g) and returns a tight value.
+//   * fe_sub(h, f, g) requires k_g <= 3 (uses f + 4p - g) and k_f <= 28 (f + 4p stays below the carry
+//     pass's 2^31; call sites pass k_f <= 2), and returns a tight value.
+//   * fe_sq(f) requires k <= 3 (19 f must fit 32 bits; call sites pass k <= 2: ge_dbl's X + Y).
+//   * fe_carry / fe_tobytes_w / fe_iszero / fe_isnegative take any limbs below 2^31 (k <= 32; call
+//     sites pass k <= 3); fe_eq(f, g) is fe_sub's: k_g <= 3 (fe_sqrt_ratio_i passes fe_neg's k = 2).
 // The same functions compile for the host (``__host__``) so tools/ can unit-test them
 // against the Python oracle; the shipped library only ever runs them on the GPU.
 #pragma once
@@ -56,7 +63,8 @@ NW_HD fe fe_add(const fe& f, const fe& g) {
     return h;
 }
 
-// One carry pass over u32 limbs (inputs up to ~2^31); result tight.
+// One carry pass over u32 limbs (every input limb < 2^31, i.e. k <= 32); result tight, and limb 6 may
+// come out at 2^26 exactly (the last carry, out of limb 5, is not propagated further).
 NW_HD void fe_carry_inplace(fe& h) {
     uint32_t c;
     c = h.v[0] >> 26; h.v[1] += c; h.v[0] &= M26;
@@ -89,7 +97,7 @@ NW_HD fe fe_sub(const fe& f, const fe& g) {
 }
 
 // h = f - g without the carry pass (k_f <= 1, g <= 4p limb-wise): limbs < 1.25 * 2^28 / 2^27,
-// i.e. k = 5.  Only valid as the FIRST operand of fe_mul with a second operand of k <= 6/... such
+// i.e. k = 5 (limb 1 up to 5 * 2^25 + 2^18 for a tight f at its bound).  Only valid as the FIRST operand of fe_mul with a second operand of k <= 6/... such
 // that k_f * k_g <= 32 (see the limb-size discipline above): 5 x 1 and 5 x 2 are used.
 NW_HD fe fe_sub_loose(const fe& f, const fe& g) {
     fe h;
@@ -115,7 +123,8 @@ NW_HD fe fe_neg(const fe& f) {
     return h;
 }
 
-// Reduce 10 u64 column sums to tight u32 limbs.
+// Reduce 10 u64 column sums to tight u32 limbs (limb 1 <= 2^25 + 2^18, limb 5 <= 2^25 + 2^13: the
+// carry out of limb 4 that follows the one INTO it, from limb 3's 64-bit column, is not propagated).
 NW_HD fe fe_reduce_wide(uint64_t h[10]) {
     uint64_t c;
     c = h[0] >> 26; h[1] += c; h[0] &= M26;
@@ -309,7 +318,7 @@ NW_HD void fe_mul4_efgh(fe& X, fe& Y, fe& Z, fe& T, const fe& e, const fe& f, co
     T = fe_fused_wrap(rt, ct);
 }
 
-// h = f^2 mod p (55 products).
+// h = f^2 mod p (55 products); k <= 3.
 NW_HD fe fe_sq(const fe& f) {
     uint64_t acc[10];
 #pragma unroll
@@ -386,7 +395,8 @@ NW_HD fe fe_invert(const fe& z) {
     return fe_mul(t1, t0);             // 2^255 - 21
 }
 
-// Canonical little-endian 8 x u32 words of f mod p.
+// Canonical little-endian 8 x u32 words of f mod p, for any limbs below 2^31 (two carry passes, then
+// the conditional subtraction of p).
 NW_HD void fe_tobytes_w(uint32_t out[8], const fe& fin) {
     fe h = fe_carry(fin);
     fe_carry_inplace(h);
