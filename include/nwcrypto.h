@@ -389,13 +389,32 @@ typedef struct nw_core_view {
     uint32_t first_vote, n_votes;    /* Certificate */
     const uint8_t* vote_keys;        /* [n_votes][32] */
     const uint8_t* vote_sigs;        /* [n_votes][64] */
+    /* A certificate whose votes are carried raw (NW_CORE_DEVICE_VOTES): n_votes is the wire count;
+     * vote_keys and vote_sigs are NULL (the votes are decoded on the device only); quorum_error is
+     * NW_DAG_OK, because the quorum rules are not evaluated on the host. */
 } nw_core_view;
+
+/* nw_core_batch_decode_ex / nw_core_messages_verify_ex flags.
+ * NW_CORE_DEVICE_VOTES: decode certificate votes on the GPU.  A certificate is taken raw (its vote
+ * section goes to the device as wire bytes; a kernel produces the signatures, signer slots and the
+ * AuthorityReuse / UnknownAuthority / RequiresQuorum / SerializationError outcome) when it is regular
+ * (every vote's key string is 44 characters long and all the votes the count announces lie inside the
+ * frame), the committee has at most 16,384 members, and after the header decode and the host checks it
+ * is still NW_DAG_PENDING with header_error == NW_DAG_OK.  Every other certificate is decoded on the
+ * host as without the flag.  Verdicts are the same with and without the flag; the batch indices are
+ * not (see nw_core_batch_verify). */
+#define NW_CORE_DEVICE_VOTES 0x1u
 
 /* Host only (no context, no GPU): decode n frames and run every host-side check of core.rs:306-346,
  * messages.rs:48-67, :131-142 and :189-215 (everything but digests and signatures). */
 int nw_core_batch_decode(const nw_committee* committee, const nw_core_state* state, const uint8_t* const* frame,
                          const size_t* len, size_t n, nw_core_batch** out);
+/* The same with flags (NW_CORE_*; 0: exactly nw_core_batch_decode; an unknown flag is NW_ERR_ARG). */
+int nw_core_batch_decode_ex(const nw_committee* committee, const nw_core_state* state, const uint8_t* const* frame,
+                            const size_t* len, size_t n, uint32_t flags, nw_core_batch** out);
 size_t nw_core_batch_size(const nw_core_batch* batch);
+/* Number of certificate votes the batch carries raw (0 without NW_CORE_DEVICE_VOTES). */
+size_t nw_core_batch_raw_votes(const nw_core_batch* batch);
 int nw_core_batch_view(const nw_core_batch* batch, size_t i, nw_core_view* out);
 void nw_core_batch_free(nw_core_batch* batch);
 /* The GPU half of core.rs:306-346 (the digests and signatures of messages.rs:48-67, :131-142,
@@ -406,13 +425,21 @@ void nw_core_batch_free(nw_core_batch* batch);
  * uses batch index cert_base + j, and *certs_used (may be NULL) receives their number, so the caller
  * advances cert_base by it.  A certificate whose header then fails on the device (id or signature)
  * still uses up its index (unlike nw_cert_batch_verify, which numbers certificates after the header
- * checks).  zseed == NULL is NW_ERR_ARG. */
+ * checks).  In a batch decoded with NW_CORE_DEVICE_VOTES the certificates that enter the batch step
+ * are those still pending with header_error == NW_DAG_OK, raw or host-decoded (a host-decoded one
+ * also needs quorum_error == NW_DAG_OK, as above); the j-th of them in arrival order uses batch index
+ * cert_base + j and *certs_used is their number.  So a raw certificate that then fails its quorum
+ * rules on the device uses up an index, where a host-decoded certificate with a quorum_error does
+ * not.  zseed == NULL is NW_ERR_ARG. */
 int nw_core_batch_verify(nw_ctx* ctx, const nw_core_batch* batch, const uint8_t zseed[32], uint64_t cert_base,
                          int32_t* verdict, uint64_t* certs_used);
 /* decode + verify + free in one call: what Core::sanitize_* (core.rs:306-346) returns per frame. */
 int nw_core_messages_verify(nw_ctx* ctx, const nw_committee* committee, const nw_core_state* state,
                             const uint8_t* const* frame, const size_t* len, size_t n, const uint8_t zseed[32],
                             uint64_t cert_base, int32_t* verdict, uint64_t* certs_used);
+int nw_core_messages_verify_ex(nw_ctx* ctx, const nw_committee* committee, const nw_core_state* state,
+                               const uint8_t* const* frame, const size_t* len, size_t n, uint32_t flags,
+                               const uint8_t zseed[32], uint64_t cert_base, int32_t* verdict, uint64_t* certs_used);
 
 /* Library build identifier (gfx target, build date). */
 const char* nw_version(void);

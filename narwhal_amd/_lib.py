@@ -57,6 +57,7 @@ DAG_MALFORMED_HEADER, DAG_UNKNOWN_AUTHORITY, DAG_AUTHORITY_REUSE, DAG_REQUIRES_Q
 DAG_NOT_CERTIFICATE = 8
 DAG_TOO_OLD, DAG_UNEXPECTED_VOTE, DAG_NOT_CORE_MESSAGE = 9, 10, 11
 CORE_HEADER, CORE_VOTE, CORE_CERTIFICATE, CORE_OTHER = 0, 1, 2, 3   # nw_core_view.kind
+CORE_DEVICE_VOTES = 0x1   # NW_CORE_DEVICE_VOTES: certificate votes decoded on the GPU
 
 
 class NwCoreState(ctypes.Structure):
@@ -77,7 +78,8 @@ ABI_VERSION = 2    # NW_ABI_VERSION of include/nwcrypto.h this binding is writte
 _OPTIONAL = {"nw_abi_version", "nw_profile_read_sigs", "nw_base_window", "nw_cert_batch_decode", "nw_cert_batch_size",
              "nw_cert_batch_view", "nw_cert_batch_free", "nw_cert_batch_verify", "nw_certificates_verify",
              "nw_sha512_many_async", "nw_job_done", "nw_job_wait", "nw_core_batch_decode", "nw_core_batch_size",
-             "nw_core_batch_view", "nw_core_batch_free", "nw_core_batch_verify", "nw_core_messages_verify"}
+             "nw_core_batch_view", "nw_core_batch_free", "nw_core_batch_verify", "nw_core_messages_verify",
+             "nw_core_batch_decode_ex", "nw_core_batch_raw_votes", "nw_core_messages_verify_ex"}
 
 
 def _load() -> ctypes.CDLL:
@@ -131,6 +133,11 @@ def _load() -> ctypes.CDLL:
         "nw_core_batch_verify": (I, [P, P, P, U64, P, ctypes.POINTER(U64)]),
         "nw_core_messages_verify": (I, [P, ctypes.POINTER(NwCommittee), ctypes.POINTER(NwCoreState), P, P, S, P, U64, P,
                                         ctypes.POINTER(U64)]),
+        "nw_core_batch_decode_ex": (I, [ctypes.POINTER(NwCommittee), ctypes.POINTER(NwCoreState), P, P, S, U32,
+                                        ctypes.POINTER(P)]),
+        "nw_core_batch_raw_votes": (S, [P]),
+        "nw_core_messages_verify_ex": (I, [P, ctypes.POINTER(NwCommittee), ctypes.POINTER(NwCoreState), P, P, S, U32, P,
+                                           U64, P, ctypes.POINTER(U64)]),
     }
     for name, (res, args) in sig.items():
         if name in _OPTIONAL and not hasattr(lib, name):
@@ -543,19 +550,25 @@ class Engine:
         return list(out[:n]), used.value
 
     def core_messages_verify(self, committee: "CommitteeABI", state: Optional[NwCoreState], frames, zseed: bytes,
-                             cert_base: int = 0):
+                             cert_base: int = 0, device_votes: bool = False):
         """nw_core_messages_verify: decode + verify + free in one ABI call; returns (verdicts,
-        certificates that used a batch index)."""
+        certificates that used a batch index).  ``device_votes``: nw_core_messages_verify_ex with
+        NW_CORE_DEVICE_VOTES (certificate votes decoded on the GPU; its own index rule)."""
         frames = [bytes(f) for f in frames]
         n = len(frames)
         ptrs = (ctypes.c_char_p * max(n, 1))(*frames)
         lens = (ctypes.c_size_t * max(n, 1))(*[len(f) for f in frames])
         out = (ctypes.c_int32 * max(n, 1))()
         used = ctypes.c_uint64(0)
-        self.check(LIB.nw_core_messages_verify(self._ctx, ctypes.byref(committee.struct),
-                                               ctypes.byref(state) if state is not None else None, ptrs, lens, n,
-                                               _buf(bytes(zseed)), cert_base, out, ctypes.byref(used)),
-                   "nw_core_messages_verify")
+        st = ctypes.byref(state) if state is not None else None
+        if device_votes:
+            self.check(LIB.nw_core_messages_verify_ex(self._ctx, ctypes.byref(committee.struct), st, ptrs, lens, n,
+                                                      CORE_DEVICE_VOTES, _buf(bytes(zseed)), cert_base, out,
+                                                      ctypes.byref(used)), "nw_core_messages_verify_ex")
+        else:
+            self.check(LIB.nw_core_messages_verify(self._ctx, ctypes.byref(committee.struct), st, ptrs, lens, n,
+                                                   _buf(bytes(zseed)), cert_base, out, ctypes.byref(used)),
+                       "nw_core_messages_verify")
         return list(out[:n]), used.value
 
 
@@ -685,19 +698,29 @@ def core_state(gc_round: int, header_id: bytes, header_round: int, header_author
 class CoreFrameBatch:
     """Host-side decode of a mixed batch of Header / Vote / Certificate frames and every host check
     of Core::sanitize_* (nw_core_batch_decode: C++, no GPU).  ``state`` None skips the checks against
-    Core's mutable state (TooOld, UnexpectedVote)."""
+    Core's mutable state (TooOld, UnexpectedVote).  ``device_votes``: nw_core_batch_decode_ex with
+    NW_CORE_DEVICE_VOTES; ``raw_votes`` is then the number of certificate votes carried as wire bytes."""
 
-    def __init__(self, committee: CommitteeABI, frames, state: Optional[NwCoreState] = None):
+    def __init__(self, committee: CommitteeABI, frames, state: Optional[NwCoreState] = None,
+                 device_votes: bool = False):
         frames = [bytes(f) for f in frames]
         n = len(frames)
         self._frames = frames
         ptrs = (ctypes.c_char_p * max(n, 1))(*frames)
         lens = (ctypes.c_size_t * max(n, 1))(*[len(f) for f in frames])
         self._h = ctypes.c_void_p()
-        rc = LIB.nw_core_batch_decode(ctypes.byref(committee.struct), ctypes.byref(state) if state is not None else None,
-                                      ptrs, lens, n, ctypes.byref(self._h))
+        st = ctypes.byref(state) if state is not None else None
+        if device_votes:
+            rc = LIB.nw_core_batch_decode_ex(ctypes.byref(committee.struct), st, ptrs, lens, n, CORE_DEVICE_VOTES,
+                                             ctypes.byref(self._h))
+        else:
+            rc = LIB.nw_core_batch_decode(ctypes.byref(committee.struct), st, ptrs, lens, n, ctypes.byref(self._h))
         if rc != NW_OK:
             raise DeviceError("nw_core_batch_decode failed (rc=%d)" % rc)
+
+    @property
+    def raw_votes(self) -> int:
+        return LIB.nw_core_batch_raw_votes(self._h)
 
     @property
     def handle(self):
@@ -714,10 +737,10 @@ class CoreFrameBatch:
         def rd(p, k):
             return ctypes.string_at(p, k) if p and k else (b"" if p else None)
         votes = None
-        if v.kind == CORE_CERTIFICATE:
+        if v.kind == CORE_CERTIFICATE and (v.vote_keys or not v.n_votes):   # NULL: the votes are carried raw
             votes = [(ctypes.string_at(v.vote_keys + 32 * j, 32), ctypes.string_at(v.vote_sigs + 64 * j, 64))
                      for j in range(v.n_votes)]
-        return {"kind": v.kind, "status": v.status, "header_error": v.header_error, "quorum_error": v.quorum_error,
+        return {"kind": v.kind, "n_votes": v.n_votes, "status": v.status, "header_error": v.header_error, "quorum_error": v.quorum_error,
                 "round": v.round, "author": rd(v.author, 32), "id": rd(v.id, 32), "origin": rd(v.origin, 32),
                 "signature": rd(v.signature, 64), "preimage": rd(v.preimage, v.preimage_len),
                 "cert_preimage": rd(v.cert_preimage, 72), "votes": votes}

@@ -188,26 +188,32 @@ def _errors(codes: Sequence[int]) -> List[Optional[DagError]]:
 
 
 def decode_core_frames(frames: Sequence[bytes], committee: Committee, gc_round: Optional[int] = None,
-                       current_header: Optional[Header] = None) -> "_lib.CoreFrameBatch":
+                       current_header: Optional[Header] = None, device_votes: bool = False) -> "_lib.CoreFrameBatch":
     """Native (C++) decode + every host check of Core::sanitize_* for a mixed batch of frames (no
-    GPU).  With ``gc_round`` None the checks against Core's state are skipped."""
+    GPU).  With ``gc_round`` None the checks against Core's state are skipped.  ``device_votes``:
+    regular certificates keep their votes as wire bytes for the GPU (NW_CORE_DEVICE_VOTES)."""
     state = None
     if gc_round is not None:
         state = _lib.core_state(gc_round, current_header.id, current_header.round, current_header.author)
-    return _lib.CoreFrameBatch(committee_abi(committee), frames, state)
+    return _lib.CoreFrameBatch(committee_abi(committee), frames, state, device_votes=device_votes)
 
 
 def sanitize_frames(frames: Sequence[bytes], committee: Committee, gc_round: int, current_header: Header,
-                    engine=None, zseed: Optional[bytes] = None, cert_base: int = 0) -> List[Optional[DagError]]:
+                    engine=None, zseed: Optional[bytes] = None, cert_base: int = 0,
+                    device_votes: bool = False) -> List[Optional[DagError]]:
     """``sanitize_messages`` on the wire frames, natively: C++ decode and host checks, then every
     digest and signature in ONE GPU submission (nw_core_messages_verify).  Returns None (Ok) or the
     DagError per frame, in the reference's check order.  Batch coefficients: the j-th certificate
-    that passes its host checks uses batch index ``cert_base + j`` (include/nwcrypto.h)."""
+    that passes its host checks uses batch index ``cert_base + j`` (include/nwcrypto.h).
+    ``device_votes``: the votes of regular certificates are decoded and checked against the quorum
+    rules on the GPU (NW_CORE_DEVICE_VOTES); same verdicts, but such a certificate uses up a batch
+    index even when it then fails its quorum rules."""
     eng = engine or _lib.default_engine()
     if zseed is None:
         zseed = os.urandom(32)
     state = _lib.core_state(gc_round, current_header.id, current_header.round, current_header.author)
-    codes, _ = eng.core_messages_verify(committee_abi(committee), state, frames, zseed, cert_base)
+    codes, _ = eng.core_messages_verify(committee_abi(committee), state, frames, zseed, cert_base,
+                                        device_votes=device_votes)
     return _errors(codes)
 
 
@@ -228,8 +234,9 @@ class CoreBatcher:
     UnexpectedVote against the current header) are evaluated when a batch is applied, against the
     state at that moment, so the results equal ``submit`` called batch after batch."""
 
-    def __init__(self, committee: Committee, engine=None, gc_depth: int = 50):
+    def __init__(self, committee: Committee, engine=None, gc_depth: int = 50, device_votes: bool = False):
         self.committee = committee
+        self.device_votes = device_votes   # submit_frames: certificate votes decoded on the GPU
         self.engine = engine or _lib.default_engine()
         self.gc_depth = gc_depth
         self.gc_round = 0
@@ -288,7 +295,7 @@ class CoreBatcher:
         if zseed is None:
             zseed = os.urandom(32)
         codes, used = self.engine.core_messages_verify(committee_abi(self.committee), None, frames, zseed,
-                                                       self.cert_base)
+                                                       self.cert_base, device_votes=self.device_votes)
         self.cert_base += used
         checked = _errors(codes)
         errs: List[Optional[DagError]] = list(checked)

@@ -12,6 +12,11 @@
 //   cvote0 / cnv / csrc       certificates that enter the batch step: vote range (in vote_sig /
 //                             vote_member), and the certificate digest their votes sign
 //   desc                      one descriptor per message (CoreDesc)
+//   raw / craw                a batch decoded with NW_CORE_DEVICE_VOTES: the vote section of every
+//                             certificate taken raw (nw_votewire.h), copied at 16-byte aligned
+//                             offsets, and per certificate of the pass its offset (CORE_NOT_RAW: a
+//                             host-decoded certificate).  A raw certificate has no entries in
+//                             vote_pk / vote_sig / vote_member: k_votes_ingest fills its rows.
 // A message whose verdict the host already knows contributes nothing but its descriptor; its
 // preimage is kept in ``cold`` for nw_core_batch_view only.
 #pragma once
@@ -25,6 +30,7 @@
 namespace nw {
 
 constexpr uint32_t CORE_NO_INDEX = 0xFFFFFFFFu;
+constexpr uint64_t CORE_NOT_RAW = ~(uint64_t)0;
 
 // Per-message descriptor read by k_core_verdict.  Every index is clamped on the device before use.
 struct CoreDesc {
@@ -58,6 +64,7 @@ struct nw_core_batch {
         size_t pre_off = 0, pre_len = 0;   // in ``pre`` (hot) or ``cold``
         uint8_t cert_pre[72] = {0};
         uint32_t first_vote = 0, n_votes = 0;
+        bool raw = false;                  // votes carried as wire bytes (n_votes of them)
     };
     std::vector<Msg> msgs;
     std::vector<uint8_t> vote_pk;        // [votes][32] of every decoded certificate (view)
@@ -73,6 +80,9 @@ struct nw_core_batch {
     std::vector<uint32_t> smember, ssrc;        // [S]
     std::vector<uint32_t> cvote0, cnv, csrc;    // [C]
     size_t cert_votes = 0;                      // sum of cnv
+    std::vector<uint8_t> raw;                   // raw vote sections, each at a 16-byte aligned offset
+    std::vector<uint64_t> craw;                 // [C] offset in ``raw``, or CORE_NOT_RAW
+    size_t raw_certs = 0, raw_votes = 0;
     std::vector<nw::CoreDesc> desc;             // [n]
     size_t pending = 0;                         // messages whose verdict needs the device
 };

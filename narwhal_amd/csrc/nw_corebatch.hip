@@ -7,7 +7,8 @@
 //                     the verify kernels read.
 //  * k_core_verdict - one lane per message: the id check (claimed id against the header digest, all
 //                     32 bytes) and the fold of host verdict, id, header_error, strict byte,
-//                     quorum_error and certificate byte into the NW_DAG_* verdict, in the order of
+//                     quorum_error (or k_votes_ingest's vote_err, nw_votes.hip, for a certificate
+//                     whose votes went up raw) and certificate byte into the NW_DAG_* verdict, in the order of
 //                     Header::verify / Vote::verify / Certificate::verify.
 //
 // Both are a few loads and stores per lane (memory latency, no arithmetic to speak of), so they are
@@ -71,11 +72,18 @@ __global__ void __launch_bounds__(kCoreBlock) k_core_verdict(CoreVerdictParams p
     if (v == NW_DAG_PENDING) {
         const int32_t header_error = (int32_t)a.y, quorum_error = (int32_t)a.z;
         const uint32_t kind = a.w, dig = b.x, id = b.y, strict = b.z, cert = b.w;
+        // a certificate whose votes were decoded on the device: k_votes_ingest's outcome stands where
+        // quorum_error stands, except that an undecodable vote key makes the whole frame undecodable
+        int32_t vote_err = NW_DAG_OK;
+        if (p.vote_err && kind == NW_CORE_CERTIFICATE && cert != CORE_NO_INDEX && p.ncerts)
+            vote_err = p.vote_err[min(cert, p.ncerts - 1)];
         bool id_ok = true;
         if (dig != CORE_NO_INDEX)   // Header, Certificate: the claimed id is the header digest
             id_ok = p.ndig && p.nids &&
                     equal32(load32(p.dig + (size_t)min(dig, p.ndig - 1) * 64), load32(p.ids + (size_t)min(id, p.nids - 1) * 32));
-        if (!id_ok) {
+        if (vote_err == NW_DAG_SERIALIZATION) {
+            v = NW_DAG_SERIALIZATION;
+        } else if (!id_ok) {
             v = NW_DAG_INVALID_HEADER_ID;
         } else if (header_error != NW_DAG_OK) {
             v = header_error;
@@ -85,6 +93,8 @@ __global__ void __launch_bounds__(kCoreBlock) k_core_verdict(CoreVerdictParams p
             v = NW_DAG_OK;
         } else if (quorum_error != NW_DAG_OK) {
             v = quorum_error;
+        } else if (vote_err != NW_DAG_OK) {
+            v = vote_err;
         } else {
             const bool ok = cert != CORE_NO_INDEX && p.ncerts && p.cert_ok[min(cert, p.ncerts - 1)] != 0;
             v = ok ? NW_DAG_OK : NW_DAG_INVALID_SIGNATURE;

@@ -6,6 +6,9 @@
 //   3. k_core_link              digests -> the strict pass's messages, the certificate messages
 //   4. strict pass              enqueue_certs, batch_mode 0: every header, vote and
 //                               certificate-header signature -> one verdict byte each
+//   4a. k_votes_ingest          only with certificates carried raw (NW_CORE_DEVICE_VOTES): their wire
+//                               vote records -> the signature and signer-slot rows the certificate pass
+//                               reads, and one quorum outcome (vote_err) per certificate
 //   5. certificate pass         enqueue_certs, batch_mode 1: the votes of the certificates that enter
 //                               the batch step -> one verdict byte per certificate
 //   6. k_core_verdict           id check + fold -> n int32 verdicts
@@ -49,7 +52,11 @@ int nw_core_batch_verify(nw_ctx* ctx, const nw_core_batch* b, const uint8_t zsee
     NW_RC(call.begin());
     Workspace* ws = call.ws;
     hipStream_t st = call.st;
-    const CoreLayout l(n, D, b->pre.size(), H, S, C, V);
+    // raw certificates: their vote sections and the device committee index ride in the same block
+    const size_t K = b->raw_certs ? b->names.size() : 0, raw_bytes = (b->raw.size() + 15) & ~(size_t)15;
+    const CoreLayout l(n, D, b->pre.size(), H, S, C, V, raw_bytes, K);
+    const VotesPlan vplan(b->raw_certs, C, V, K);
+    if (b->raw_certs && !vplan.grid) return NW_ERR_ARG;
     // the two signature passes lay their scratch over one block, sized for the larger
     const CoreScratch cs(l, S, C, V, ctx->nkeys, ctx->finish_k);
     NW_TRY(ws->reserve(l.device_bytes(), cs.bytes(), l.pinned_bytes()), "workspace");
@@ -82,9 +89,33 @@ int nw_core_batch_verify(nw_ctx* ctx, const nw_core_batch* b, const uint8_t zsee
     for (size_t c = 0; c < C; ++c) {
         const size_t from = b->cvote0[c], nv = b->cnv[c];
         cfirst[c] = (uint32_t)v0;
-        put(l.vsig + v0 * 64, b->vote_sig.data() + from * 64, nv * 64);
-        for (size_t v = 0; v < nv; ++v) vslot[v0 + v] = slot[b->vote_member[from + v]];
+        if (b->craw[c] == CORE_NOT_RAW) {
+            put(l.vsig + v0 * 64, b->vote_sig.data() + from * 64, nv * 64);
+            for (size_t v = 0; v < nv; ++v) vslot[v0 + v] = slot[b->vote_member[from + v]];
+        }   // else k_votes_ingest writes these rows
         v0 += nv;
+    }
+    uint64_t quorum = 0;
+    if (K) {
+        put(l.raw, b->raw.data(), b->raw.size());
+        put(l.raw_off, b->craw.data(), C * 8);
+        put(l.cnames, b->names.data(), K * 32);
+        put(l.cstake, b->stakes.data(), K * 4);
+        put(l.cslot, slot.data(), K * 4);
+        // CommitteeIndex's rules: the first of duplicate names wins (stake 0 is decided on the device)
+        const uint32_t T = vw_table_size((uint32_t)K);
+        uint32_t* table = reinterpret_cast<uint32_t*>(h + l.ctable);
+        std::fill(table, table + T, CORE_NO_INDEX);
+        uint64_t total = 0;
+        for (size_t i = 0; i < K; ++i) {
+            total += b->stakes[i];
+            uint32_t w[2];
+            std::memcpy(w, b->names[i].data(), 8);
+            uint32_t at = vw_name_hash(w[0], w[1]) & (T - 1);
+            while (table[at] != CORE_NO_INDEX && b->names[table[at]] != b->names[i]) at = (at + 1) & (T - 1);
+            if (table[at] == CORE_NO_INDEX) table[at] = (uint32_t)i;
+        }
+        quorum = 2 * total / 3 + 1;   // Committee::quorum_threshold (config/src/lib.rs:189-194)
     }
     if (l.s_staged) prestage(h + l.spre, l.spl, sfn, sfn + 1, 1, S);
     if (l.c_staged) prestage(h + l.cpre, l.cpl, cfirst, b->cnv.data(), C, V);
@@ -125,6 +156,29 @@ int nw_core_batch_verify(nw_ctx* ctx, const nw_core_batch* b, const uint8_t zsee
         cc.sig_ok = d_work + l.sok;
         NW_RC(enqueue_certs(ctx, ws, cc, cs.strict_plan, cs.strict, st));
     }
+    // 4a. the votes of the raw certificates -> their rows of vsig / vslot, and vote_err
+    if (vplan.grid) {
+        VotesParams vq{};
+        vq.ncerts = (uint32_t)C;
+        vq.nsigs = (uint32_t)V;
+        vq.K = (uint32_t)K;
+        vq.tsize = vw_table_size((uint32_t)K);
+        vq.nkeys = (uint32_t)ctx->nkeys;
+        vq.raw_bytes = raw_bytes;
+        vq.quorum = quorum;
+        vq.raw = d_in + l.raw;
+        vq.raw_off = reinterpret_cast<const uint64_t*>(d_in + l.raw_off);
+        vq.first = reinterpret_cast<const uint32_t*>(d_in + l.cfirst);
+        vq.nv = reinterpret_cast<const uint32_t*>(d_in + l.cnv);
+        vq.names = d_in + l.cnames;
+        vq.stake = reinterpret_cast<const uint32_t*>(d_in + l.cstake);
+        vq.slot = reinterpret_cast<const uint32_t*>(d_in + l.cslot);
+        vq.table = reinterpret_cast<const uint32_t*>(d_in + l.ctable);
+        vq.sig = d_in + l.vsig;
+        vq.signer = reinterpret_cast<uint32_t*>(d_in + l.vslot);
+        vq.vote_err = reinterpret_cast<int32_t*>(d_work + l.verr);
+        NW_TRY(launch_votes_ingest(vq, vplan.grid, vplan.wg, vplan.lds, st), "k_votes_ingest");
+    }
     // 5. certificate pass: certificate j draws its coefficients at batch index cert_base + j
     if (C) {
         CertCall cc;
@@ -154,6 +208,7 @@ int nw_core_batch_verify(nw_ctx* ctx, const nw_core_batch* b, const uint8_t zsee
     vp.ids = d_in + l.ids;
     vp.strict_ok = d_work + l.sok;
     vp.cert_ok = d_work + l.cok;
+    vp.vote_err = vplan.grid ? reinterpret_cast<const int32_t*>(d_work + l.verr) : nullptr;
     vp.verdict = reinterpret_cast<int32_t*>(d_out + l.verdict);
     NW_TRY(launch_core_verdict(vp, st), "k_core_verdict");
     // 7. the H2D above has completed in stream order before this copy overwrites the staging buffer
@@ -166,8 +221,14 @@ int nw_core_batch_verify(nw_ctx* ctx, const nw_core_batch* b, const uint8_t zsee
 int nw_core_messages_verify(nw_ctx* ctx, const nw_committee* cm, const nw_core_state* state, const uint8_t* const* frame,
                             const size_t* len, size_t n, const uint8_t zseed[32], uint64_t cert_base, int32_t* verdict,
                             uint64_t* certs_used) {
+    return nw_core_messages_verify_ex(ctx, cm, state, frame, len, n, 0, zseed, cert_base, verdict, certs_used);
+}
+
+int nw_core_messages_verify_ex(nw_ctx* ctx, const nw_committee* cm, const nw_core_state* state,
+                               const uint8_t* const* frame, const size_t* len, size_t n, uint32_t flags,
+                               const uint8_t zseed[32], uint64_t cert_base, int32_t* verdict, uint64_t* certs_used) {
     nw_core_batch* b = nullptr;
-    int rc = nw_core_batch_decode(cm, state, frame, len, n, &b);
+    int rc = nw_core_batch_decode_ex(cm, state, frame, len, n, flags, &b);
     if (rc != NW_OK) return rc;
     rc = nw_core_batch_verify(ctx, b, zseed, cert_base, verdict, certs_used);
     nw_core_batch_free(b);

@@ -17,6 +17,7 @@
 
 #include "nw_kernels.h"
 #include "nw_msm.h"
+#include "nw_votewire.h"
 
 namespace nw {
 
@@ -126,6 +127,12 @@ struct CertsLayout {
 //         lengths, the certificate messages, the verdict bytes of both passes
 //   out   behind ``work``: the n int32 verdicts (one D2H)
 // Every segment is 256-byte aligned, so every 32-byte value in it is 32-byte aligned.
+// A batch with raw certificates (NW_CORE_DEVICE_VOTES: raw_bytes of wire vote sections, a committee
+// of K > 0 members) adds, behind the segments above and with size 0 otherwise: to ``in`` the raw
+// regions, their per-certificate offsets and the device committee index (names, stakes, key-cache
+// slots, the open-addressing table of vw_table_size(K) member indices); to ``work`` the int32
+// vote_err per certificate that k_votes_ingest writes.  K == 0 gives exactly the block of a batch
+// without raw votes.
 struct CoreLayout {
     bool s_staged, c_staged;
     PreLayout spl, cpl;
@@ -133,14 +140,20 @@ struct CoreLayout {
     size_t desc, pre, dig_off, dig_len, ids, ssig, sslot, ssrc, sfn, cfirst, cnv, csrc, vsig, vslot, spre, cpre;
     size_t dig, smsg, smsg_off, smsg_len, cmsg, sok, cok;
     size_t verdict;
-    CoreLayout(size_t n, size_t D, size_t pre_bytes, size_t H, size_t S, size_t C, size_t V)
+    size_t raw, raw_off, cnames, cstake, cslot, ctable;   // in, behind cpre
+    size_t verr;                                          // work, behind cok
+    CoreLayout(size_t n, size_t D, size_t pre_bytes, size_t H, size_t S, size_t C, size_t V, size_t raw_bytes = 0,
+               size_t K = 0)
         : s_staged(S > 0 && S <= kStagedMaxSigs), c_staged(C > 0 && V <= kStagedMaxSigs), spl(S, 1), cpl(V, C),
           desc(in.take(n * 32)), pre(in.take(pre_bytes + 8)), dig_off(in.take(D * 8)), dig_len(in.take(D * 8)),
           ids(in.take(H * 32)), ssig(in.take(S * 64)), sslot(in.take(S * 4)), ssrc(in.take(S * 4)), sfn(in.take(8)),
           cfirst(in.take(C * 4)), cnv(in.take(C * 4)), csrc(in.take(C * 4)), vsig(in.take(V * 64)),
           vslot(in.take(V * 4)), spre(in.take(s_staged ? spl.bytes() : 0)), cpre(in.take(c_staged ? cpl.bytes() : 0)),
           dig(work.take(D * 64)), smsg(work.take(S * 32 + 8)), smsg_off(work.take(S * 8)), smsg_len(work.take(S * 8)),
-          cmsg(work.take(C * 32)), sok(work.take(S)), cok(work.take(C)), verdict(out.take(n * 4)) {}
+          cmsg(work.take(C * 32)), sok(work.take(S)), cok(work.take(C)), verdict(out.take(n * 4)),
+          raw(in.take(K ? raw_bytes : 0)), raw_off(in.take(K ? C * 8 : 0)), cnames(in.take(K * 32)),
+          cstake(in.take(K * 4)), cslot(in.take(K * 4)), ctable(in.take(K ? (size_t)vw_table_size((uint32_t)K) * 4 : 0)),
+          verr(work.take(K ? C * 4 : 0)) {}
     size_t work_at() const { return in.end; }              // device offsets of the other two blocks
     size_t out_at() const { return in.end + work.end; }
     size_t device_bytes() const { return in.end + work.end + out.end; }
@@ -200,6 +213,21 @@ inline FinishPlan finish_plan(uint32_t pinned_fk, size_t n, bool may_fuse) {
     f.grid = blocks_for(lanes, f.fk == 1 ? 256 : FINISH_WG);
     return f;
 }
+
+// k_votes_ingest (nw_votes.hip) over the C certificates of a mixed Core batch's certificate pass, V
+// votes in all, against a committee of K members: one workgroup per certificate, sized from the
+// average vote count as the finalize is (a performance choice only: lanes stride over the votes);
+// dynamic LDS: a few control words and one first-position word per member.  Not launched (grid 0) without raw certificates.
+struct VotesPlan {
+    uint32_t grid = 0, wg = 0, lds = 0;
+    VotesPlan(size_t raw_certs, size_t C, size_t V, size_t K) {
+        if (!raw_certs || !C || !K || K > kDeviceVotesMaxCommittee) return;
+        const size_t avg_votes = V / C;
+        grid = (uint32_t)C;
+        wg = avg_votes > 512 ? VOTES_MAX_WG : (avg_votes > 64 ? 256u : 64u);
+        lds = VOTES_LDS_HEAD + (uint32_t)K * 4;
+    }
+};
 
 // One run of the certificate pipeline (enqueue_certs) over ncerts certificates and nsigs
 // signatures against a cache of nkeys keys.  prestaged: the caller uploaded the preamble state

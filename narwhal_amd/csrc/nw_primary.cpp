@@ -29,6 +29,7 @@
 
 #include "../../include/nwcrypto.h"
 #include "nw_corebatch.h"
+#include "nw_votewire.h"
 
 namespace {
 
@@ -259,12 +260,10 @@ struct DecodeScratch {
 // Certificate::verify: fills record c of batch b (a nw_cert_batch or a nw_core_batch: the votes go
 // to b's vote arrays) and sets c.status to SERIALIZATION, OK (genesis) or leaves it PENDING with
 // header_error / quorum_error set.
+//
+// The part after the header: the votes and the host checks (t.workers: the header's worker ids).
 template <class Batch, class Rec>
-void read_certificate(Reader& r, const CommitteeIndex& ci, Batch* b, Rec& c, DecodeScratch& t) {
-    if (!read_header(r, c, t.workers, t.b64)) {
-        c.status = NW_DAG_SERIALIZATION;
-        return;
-    }
+void read_certificate_votes(Reader& r, const CommitteeIndex& ci, Batch* b, Rec& c, DecodeScratch& t) {
     const uint64_t nv = r.u64();
     if (!r.ok || nv > (r.n - r.at) / 72) {   // each vote takes >= 8 + 64 bytes
         c.status = NW_DAG_SERIALIZATION;
@@ -324,6 +323,15 @@ void read_certificate(Reader& r, const CommitteeIndex& ci, Batch* b, Rec& c, Dec
         weight += st;
     }
     if (c.quorum_error == NW_DAG_OK && weight < ci.quorum) c.quorum_error = NW_DAG_REQUIRES_QUORUM;
+}
+
+template <class Batch, class Rec>
+void read_certificate(Reader& r, const CommitteeIndex& ci, Batch* b, Rec& c, DecodeScratch& t) {
+    if (!read_header(r, c, t.workers, t.b64)) {
+        c.status = NW_DAG_SERIALIZATION;
+        return;
+    }
+    read_certificate_votes(r, ci, b, c, t);
 }
 
 bool committee_ok(const nw_committee* cm) { return cm && !(cm->n && (!cm->name || !cm->stake)); }
@@ -545,8 +553,53 @@ bool read_certificates_request(Reader& r, DecodeScratch& t) {
     return r.public_key(requestor, t.b64);
 }
 
-void decode_core_message(nw_core_batch* b, const CommitteeIndex& ci, const nw_core_state* st, Reader& r, Msg& m,
-                         nw::CoreDesc& d, DecodeScratch& t) {
+void enter_cert_pass(nw_core_batch* b, Msg& m, nw::CoreDesc& d, uint64_t raw_at) {
+    d.cert = (uint32_t)b->cnv.size();
+    b->cvote0.push_back(m.first_vote);
+    b->cnv.push_back(m.n_votes);
+    b->craw.push_back(raw_at);
+    b->csrc.push_back(add_digest(b, pack(b->pre, m.cert_pre, 72), 72));
+    b->cert_votes += m.n_votes;
+}
+
+// NW_CORE_DEVICE_VOTES: the certificate whose header was just read keeps its votes as wire bytes
+// when it is regular (nw_votewire.h: walking the len fields only), the committee fits the device
+// index, and it would enter the certificate pass but for the quorum rules: not stale, not genesis,
+// header_error OK.  Returns false with the reader where it was: today's reader takes the votes (so
+// a stale certificate with an undecodable vote key is still a serialization error).
+bool take_raw_votes(nw_core_batch* b, const CommitteeIndex& ci, const nw_core_state* st, const Reader& r0, Msg& m,
+                    nw::CoreDesc& d, DecodeScratch& t) {
+    if (ci.cm->n > nw::kDeviceVotesMaxCommittee) return false;
+    Reader r = r0;
+    const uint64_t nv = r.u64();
+    if (!r.ok || nv > (r.n - r.at) / nw::kVoteRecord || nv > 0xFFFFFFF0u) return false;
+    const uint8_t* votes = r.p + r.at;
+    for (uint64_t v = 0; v < nv; ++v) {
+        uint64_t len;
+        std::memcpy(&len, votes + v * nw::kVoteRecord, 8);
+        if (len != nw::kVoteKeyChars) return false;
+    }
+    if (st && st->gc_round > m.round) return false;
+    static const uint8_t zero[32] = {0};
+    if (m.round == 0 && std::memcmp(m.id, zero, 32) == 0 && ci.member.count(m.author)) return false;   // genesis
+    if (ci.header_error(m.author, t.workers) != NW_DAG_OK) return false;
+    m.kind = NW_CORE_CERTIFICATE;
+    m.origin = m.author;
+    m.raw = true;
+    m.n_votes = (uint32_t)nv;
+    std::memcpy(m.cert_pre, m.id, 32);
+    std::memcpy(m.cert_pre + 32, &m.round, 8);
+    std::memcpy(m.cert_pre + 40, m.author.data(), 32);
+    const uint64_t at = pack(b->raw, votes, (size_t)nv * nw::kVoteRecord);
+    ++b->raw_certs;
+    b->raw_votes += (size_t)nv;
+    add_header(b, ci, m, d);
+    enter_cert_pass(b, m, d, at);
+    return true;
+}
+
+void decode_core_message(nw_core_batch* b, const CommitteeIndex& ci, const nw_core_state* st, uint32_t flags, Reader& r,
+                         Msg& m, nw::CoreDesc& d, DecodeScratch& t) {
     const uint32_t tag = r.u32();
     if (!r.ok || tag > 3) {
         m.status = NW_DAG_SERIALIZATION;
@@ -607,7 +660,12 @@ void decode_core_message(nw_core_batch* b, const CommitteeIndex& ci, const nw_co
         return;
     }
     // Certificate: sanitize_certificate (core.rs:338-346)
-    read_certificate(r, ci, b, m, t);
+    if (!read_header(r, m, t.workers, t.b64)) {
+        m.status = NW_DAG_SERIALIZATION;
+        return;
+    }
+    if ((flags & NW_CORE_DEVICE_VOTES) && take_raw_votes(b, ci, st, r, m, d, t)) return;
+    read_certificate_votes(r, ci, b, m, t);
     if (m.status == NW_DAG_SERIALIZATION) return;
     m.kind = NW_CORE_CERTIFICATE;
     m.origin = m.author;
@@ -617,13 +675,8 @@ void decode_core_message(nw_core_batch* b, const CommitteeIndex& ci, const nw_co
         return;
     }
     add_header(b, ci, m, d);
-    if (m.header_error == NW_DAG_OK && m.quorum_error == NW_DAG_OK) {   // enters the batch step
-        d.cert = (uint32_t)b->cnv.size();
-        b->cvote0.push_back(m.first_vote);
-        b->cnv.push_back(m.n_votes);
-        b->csrc.push_back(add_digest(b, pack(b->pre, m.cert_pre, 72), 72));
-        b->cert_votes += m.n_votes;
-    }
+    if (m.header_error == NW_DAG_OK && m.quorum_error == NW_DAG_OK)   // enters the batch step
+        enter_cert_pass(b, m, d, nw::CORE_NOT_RAW);
 }
 
 }  // namespace
@@ -632,7 +685,12 @@ extern "C" {
 
 int nw_core_batch_decode(const nw_committee* cm, const nw_core_state* st, const uint8_t* const* frame, const size_t* len,
                          size_t n, nw_core_batch** out) {
-    if (!out || !committee_ok(cm) || (n && (!frame || !len))) return NW_ERR_ARG;
+    return nw_core_batch_decode_ex(cm, st, frame, len, n, 0, out);
+}
+
+int nw_core_batch_decode_ex(const nw_committee* cm, const nw_core_state* st, const uint8_t* const* frame,
+                            const size_t* len, size_t n, uint32_t flags, nw_core_batch** out) {
+    if (!out || !committee_ok(cm) || (n && (!frame || !len)) || (flags & ~NW_CORE_DEVICE_VOTES)) return NW_ERR_ARG;
     *out = nullptr;
     for (size_t i = 0; i < n; ++i)
         if (!frame[i] && len[i]) return NW_ERR_ARG;
@@ -647,7 +705,7 @@ int nw_core_batch_decode(const nw_committee* cm, const nw_core_state* st, const 
         nw::CoreDesc& d = b->desc[i];
         d.dig = d.id = d.strict = d.cert = nw::CORE_NO_INDEX;
         Reader r{frame[i], len[i]};
-        decode_core_message(b, ci, st, r, m, d, t);
+        decode_core_message(b, ci, st, flags, r, m, d, t);
         std::vector<uint8_t>().swap(m.header_pre);   // packed into pre / cold
         d.status = m.status;
         d.header_error = m.header_error;
@@ -662,6 +720,8 @@ int nw_core_batch_decode(const nw_committee* cm, const nw_core_state* st, const 
 void nw_core_batch_free(nw_core_batch* b) { delete b; }
 
 size_t nw_core_batch_size(const nw_core_batch* b) { return b ? b->msgs.size() : 0; }
+
+size_t nw_core_batch_raw_votes(const nw_core_batch* b) { return b ? b->raw_votes : 0; }
 
 int nw_core_batch_view(const nw_core_batch* b, size_t i, nw_core_view* out) {
     if (!b || !out || i >= b->msgs.size()) return NW_ERR_ARG;
@@ -685,8 +745,10 @@ int nw_core_batch_view(const nw_core_batch* b, size_t i, nw_core_view* out) {
         out->cert_preimage = m.cert_pre;
         out->first_vote = m.first_vote;
         out->n_votes = m.n_votes;
-        out->vote_keys = b->vote_pk.data() + (size_t)m.first_vote * 32;
-        out->vote_sigs = b->vote_sig.data() + (size_t)m.first_vote * 64;
+        if (!m.raw) {   // a raw certificate's votes are wire bytes: decoded on the device only
+            out->vote_keys = b->vote_pk.data() + (size_t)m.first_vote * 32;
+            out->vote_sigs = b->vote_sig.data() + (size_t)m.first_vote * 64;
+        }
     }
     return NW_OK;
 }

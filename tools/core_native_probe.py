@@ -1,11 +1,16 @@
-"""Wall time of one mixed Core batch check on three paths, in one process after a warm-up:
+"""Wall time of one mixed Core batch check on four paths, in one process after a warm-up:
   (a) core.sanitize_messages on message objects  (Python batching: five GPU submissions)
   (b) primary.verify_certificate_frames          (native, the batch's certificates only: three submissions)
   (c) core.sanitize_frames on wire frames        (native, one submission: nw_core_messages_verify)
-over four batches: one header; one header + one vote + one certificate; a 60-message mixed batch (7
-validators); a 3,000-message mixed batch (100 validators, 67-vote certificates).  Every path is
-checked to give the same verdicts as (a) before it is timed.  Prints one JSON line per batch with the
-p50 / p90 of --calls calls per path, and writes them all to --out.
+  (d) core.sanitize_frames(device_votes=True)    ((c) with the certificate votes decoded on the GPU:
+                                                 NW_CORE_DEVICE_VOTES, k_votes_ingest)
+over five batches: one header; one header + one vote + one certificate; a 60-message mixed batch (7
+validators); a 3,000-message mixed batch (100 validators, 67-vote certificates); three certificates
+of 6,667 votes from a 10,000-member committee (the shape of one C4 certificate, small enough for a
+probe).  Every path is checked to give the same verdicts as (a) before it is timed.  Prints one JSON
+line per batch with the p50 / p90 of --calls calls per path and (d) / (c), and writes them all to
+--out.  Also times the two host-only decode calls (nw_core_batch_decode with and without the flag)
+on each batch's frames.
 Usage (on an MI355X): python tools/core_native_probe.py --calls 200 --out core_native.json"""
 import argparse
 import hashlib
@@ -95,8 +100,12 @@ def main():
     shapes = [("one header", 7, 1, ["header"]), ("header + vote + certificate", 7, 3, None), ("mixed 60", 7, 60, None)]
     if not args.skip_large:
         shapes.append(("mixed 3000", 100, 3000, None))
+        shapes.append(("3 certificates of 6667", 10000, 3, ["certificate"]))
     results = []
+    small_eng = eng
     for name, nval, n, only in shapes:
+        # a key cache sizes itself at its first load: the large committee gets an engine of its own
+        eng = _lib.Engine(device=0) if nval > 1000 else small_eng
         com, own, msgs = build(eng, nval, n, 11, only)
         frames = [pm.encode_primary_message(m) for m in msgs]
         cert_frames = [f for f, m in zip(frames, msgs) if isinstance(m, pm.Certificate)]
@@ -106,18 +115,38 @@ def main():
         got = kinds(core.sanitize_frames(frames, com, 5, own, eng, zseed))
         if got != want:
             raise SystemExit("%s: sanitize_frames != sanitize_messages" % name)
+        got = kinds(core.sanitize_frames(frames, com, 5, own, eng, zseed, device_votes=True))
+        if got != want:
+            raise SystemExit("%s: sanitize_frames(device_votes=True) != sanitize_messages" % name)
+        raw = core.decode_core_frames(frames, com, 5, own, device_votes=True)
+        raw_votes = raw.raw_votes
+        raw.close()
+        slow = nval > 1000   # the Python object path takes seconds per call there
         row = {"batch": name, "validators": nval, "messages": n, "certificates": len(cert_frames),
                "certificate_votes": sum(len(m.votes) for m in msgs if isinstance(m, pm.Certificate)),
                "verdicts": {str(k): want.count(k) for k in sorted(set(want), key=str)},
+               "raw_votes": raw_votes,
                "a_sanitize_messages": timed(lambda: core.sanitize_messages(msgs, com, 5, own, eng, zseed),
-                                            args.calls, args.warmup),
+                                            max(3, args.calls // 20) if slow else args.calls, 1 if slow else args.warmup),
                "c_sanitize_frames": timed(lambda: core.sanitize_frames(frames, com, 5, own, eng, zseed),
-                                          args.calls, args.warmup)}
+                                          args.calls, args.warmup),
+               "d_sanitize_frames_device_votes": timed(
+                   lambda: core.sanitize_frames(frames, com, 5, own, eng, zseed, device_votes=True),
+                   args.calls, args.warmup),
+               "decode_host": timed(lambda: core.decode_core_frames(frames, com, 5, own).close(),
+                                    args.calls, args.warmup),
+               "decode_device_votes": timed(lambda: core.decode_core_frames(frames, com, 5, own, device_votes=True).close(),
+                                            args.calls, args.warmup)}
+        row["d_over_c_p50"] = row["d_sanitize_frames_device_votes"]["p50_ms"] / row["c_sanitize_frames"]["p50_ms"]
+        row["c_p90_minus_p50_ms"] = row["c_sanitize_frames"]["p90_ms"] - row["c_sanitize_frames"]["p50_ms"]
         if cert_frames:
             row["b_verify_certificate_frames"] = timed(
                 lambda: pm.verify_certificate_frames(cert_frames, com, eng, zseed), args.calls, args.warmup)
         results.append(row)
         print(json.dumps(row), flush=True)
+        if eng is not small_eng:
+            eng.close()
+    eng = small_eng
     if args.out:
         with open(args.out, "w") as f:
             json.dump({"library": _lib.version(), "results": results}, f, indent=1)
