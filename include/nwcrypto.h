@@ -239,7 +239,9 @@ int nw_sha512_many_dev(nw_ctx* ctx, const uint8_t* d_base, const uint64_t* d_off
  *                     job must be waited for exactly once, before nw_ctx_destroy.
  * A job holds one of the context's 64 call workspaces until it is waited for; at most 32 jobs may be
  * unwaited at once (the rest of the pool stays for synchronous calls): a 33rd submit returns
- * NW_ERR_NOMEM at once rather than blocking. */
+ * NW_ERR_NOMEM at once rather than blocking.  nw_job_done and nw_job_wait serve the Core jobs of
+ * nw_core_batch_verify_async as well (nw_job_wait then fills n x 4 verdict bytes), and the limit of
+ * 32 counts the jobs of both kinds together. */
 typedef struct nw_job nw_job;
 int nw_sha512_many_async(nw_ctx* ctx, const uint8_t* const* msg, const size_t* len, size_t n,
                          uint8_t (*out)[64], nw_job** job);
@@ -440,6 +442,94 @@ int nw_core_messages_verify(nw_ctx* ctx, const nw_committee* committee, const nw
 int nw_core_messages_verify_ex(nw_ctx* ctx, const nw_committee* committee, const nw_core_state* state,
                                const uint8_t* const* frame, const size_t* len, size_t n, uint32_t flags,
                                const uint8_t zseed[32], uint64_t cert_base, int32_t* verdict, uint64_t* certs_used);
+
+/* Asynchronous form of nw_core_batch_verify, for a Core that keeps receiving while a batch is checked
+ * (the reference's Core::run awaits each sanitize_* in its one task, primary/src/core.rs:351-389):
+ * the same checks, the same submission and the same batch indices, but the call returns a job once
+ * the work is enqueued.  *certs_used is written before it returns, so the next batch can be submitted
+ * at cert_base + *certs_used while this one is in flight.  batch and zseed may be freed as soon as it
+ * returns; verdict (n x int32) must stay valid until nw_job_wait(job), which fills it and frees the
+ * job.  nw_job_done polls.  Every job must be waited for exactly once, before nw_ctx_destroy; Core
+ * and digest jobs share the limit of 32 unwaited jobs (a 33rd submit: NW_ERR_NOMEM at once, nothing
+ * enqueued).  A batch the host decided completely yields a job that is already complete: verdict is
+ * filled on return, ctx may be NULL, and the job still has to be waited for (which only frees it).
+ * A job reads the key cache: an nw_committee_load that adds keys or changes a stake while jobs are in
+ * flight first waits for them on the device (it needs no nw_job_wait to have been called). */
+int nw_core_batch_verify_async(nw_ctx* ctx, const nw_core_batch* batch, const uint8_t zseed[32], uint64_t cert_base,
+                               int32_t* verdict, uint64_t* certs_used, nw_job** job);
+/* decode (flags as nw_core_batch_decode_ex) + nw_core_batch_verify_async + free in one call; the frames
+ * may be freed on return. */
+int nw_core_messages_verify_async(nw_ctx* ctx, const nw_committee* committee, const nw_core_state* state,
+                                  const uint8_t* const* frame, const size_t* len, size_t n, uint32_t flags,
+                                  const uint8_t zseed[32], uint64_t cert_base, int32_t* verdict,
+                                  uint64_t* certs_used, nw_job** job);
+
+/* ---- Core apply: the aggregators (host only, no context, no GPU) ---------------------------------
+ * The half of ``Core`` that consumes the verdicts (primary/src/core.rs:216-247 process_vote, :285-296
+ * process_certificate, :117-120 process_own_header, :399-409 the gc cleanup; VotesAggregator and
+ * CertificatesAggregator, primary/src/aggregators.rs:9-45 and :48-83), driven batch by batch.
+ *
+ * nw_core_agg_apply takes a batch decoded with a NULL state and its checked verdicts (what
+ * nw_core_batch_verify or nw_job_wait wrote) and walks the messages in arrival order:
+ *   - a frame whose verdict is NW_DAG_SERIALIZATION or NW_DAG_NOT_CORE_MESSAGE keeps it and takes no
+ *     further part;
+ *   - every other message first meets the state checks of core.rs:307-310, :321-333, :339-342 against
+ *     the aggregator's state AT THAT MOMENT (gc_round, the current header); NW_DAG_TOO_OLD /
+ *     NW_DAG_UNEXPECTED_VOTE replace the checked verdict;
+ *   - an accepted vote (NW_DAG_OK) goes to the votes aggregator of the current header: a repeated
+ *     author is NW_DAG_AUTHORITY_REUSE in verdict[i]; otherwise the vote is recorded, and when the
+ *     weight reaches the quorum threshold it is reset to 0 (quorum is reached once), an
+ *     NW_CORE_EVENT_CERT_ASSEMBLED event lists the recorded votes, and the assembled certificate goes
+ *     at once to the certificates aggregator of the current header's round, origin = its author;
+ *   - an accepted certificate goes to its round's certificates aggregator: a repeated origin is
+ *     ignored; otherwise it is gathered, and at or past the quorum threshold an NW_CORE_EVENT_PARENTS
+ *     event lists everything gathered since the last event of that round.  The weight stays (the
+ *     reference's reset is commented out, aggregators.rs:79), so every later distinct origin triggers
+ *     again.
+ * A member without stake counts as unknown (stake 0); of duplicate names the first holds the stake.
+ *
+ * Events refer to frames, which the caller keeps: (tag, index) = (the tag given to the apply call that
+ * saw the frame, its index in that batch).  The library keeps no message bytes beyond 32-byte names.
+ *   CERT_ASSEMBLED  refs[first .. first + count): the votes, in the order recorded (possibly from
+ *                   earlier batches); round = the current header's.
+ *   PARENTS         refs[first .. first + count): the certificates; one assembled from votes is the
+ *                   (tag, index) of the vote that completed it, with assembled = 1; round = theirs.
+ * Events, and the refs array (nw_core_agg_refs), stay valid until the next nw_core_agg_apply or
+ * nw_core_agg_destroy.  Not thread-safe: one aggregator belongs to one Core. */
+#define NW_CORE_EVENT_CERT_ASSEMBLED 1
+#define NW_CORE_EVENT_PARENTS 2
+
+typedef struct nw_core_agg nw_core_agg;
+
+typedef struct nw_core_ref {
+    uint64_t tag;          /* of the batch that carried the frame */
+    uint32_t index;        /* of the frame in that batch */
+    uint32_t assembled;    /* PARENTS: 1 = the certificate assembled when this vote arrived */
+} nw_core_ref;
+
+typedef struct nw_core_event {
+    int32_t kind;          /* NW_CORE_EVENT_* */
+    uint64_t round;
+    uint64_t tag;          /* batch and ... */
+    uint32_t at;           /* ... message that triggered the event */
+    uint32_t first, count; /* range of nw_core_agg_refs */
+} nw_core_event;
+
+/* gc_depth as in Core (core.rs:44).  The state starts as Core's: gc_round 0, a current header of
+ * round 0 with an all-zero id and author. */
+int nw_core_agg_create(const nw_committee* committee, uint64_t gc_depth, nw_core_agg** out);
+void nw_core_agg_destroy(nw_core_agg* agg);
+/* process_own_header (core.rs:117-120): the current header, and a fresh votes aggregator. */
+int nw_core_agg_set_header(nw_core_agg* agg, const uint8_t id[32], uint64_t round, const uint8_t author[32]);
+/* The cleanup of core.rs:399-409: for consensus_round > gc_depth, gc_round = consensus_round -
+ * gc_depth and the certificates aggregators of rounds below it are dropped. */
+int nw_core_agg_advance_gc(nw_core_agg* agg, uint64_t consensus_round);
+int nw_core_agg_state(const nw_core_agg* agg, nw_core_state* out);
+/* verdict: in, the checked verdicts; out, the final ones.  *events / *n_events: this call's events in
+ * the order they happened (either may be NULL).  NW_ERR_ARG when a verdict is NW_DAG_PENDING. */
+int nw_core_agg_apply(nw_core_agg* agg, const nw_core_batch* batch, uint64_t tag, int32_t* verdict,
+                      const nw_core_event** events, size_t* n_events);
+int nw_core_agg_refs(const nw_core_agg* agg, const nw_core_ref** refs, size_t* n);
 
 /* Library build identifier (gfx target, build date). */
 const char* nw_version(void);

@@ -73,13 +73,29 @@ class NwCoreView(ctypes.Structure):
                 ("first_vote", ctypes.c_uint32), ("n_votes", ctypes.c_uint32), ("vote_keys", ctypes.c_void_p),
                 ("vote_sigs", ctypes.c_void_p)]
 
+
+CORE_EVENT_CERT_ASSEMBLED, CORE_EVENT_PARENTS = 1, 2   # nw_core_event.kind
+
+
+class NwCoreRef(ctypes.Structure):
+    _fields_ = [("tag", ctypes.c_uint64), ("index", ctypes.c_uint32), ("assembled", ctypes.c_uint32)]
+
+
+class NwCoreEvent(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int32), ("round", ctypes.c_uint64), ("tag", ctypes.c_uint64),
+                ("at", ctypes.c_uint32), ("first", ctypes.c_uint32), ("count", ctypes.c_uint32)]
+
+
 ABI_VERSION = 2    # NW_ABI_VERSION of include/nwcrypto.h this binding is written against
 
 _OPTIONAL = {"nw_abi_version", "nw_profile_read_sigs", "nw_base_window", "nw_cert_batch_decode", "nw_cert_batch_size",
              "nw_cert_batch_view", "nw_cert_batch_free", "nw_cert_batch_verify", "nw_certificates_verify",
              "nw_sha512_many_async", "nw_job_done", "nw_job_wait", "nw_core_batch_decode", "nw_core_batch_size",
              "nw_core_batch_view", "nw_core_batch_free", "nw_core_batch_verify", "nw_core_messages_verify",
-             "nw_core_batch_decode_ex", "nw_core_batch_raw_votes", "nw_core_messages_verify_ex"}
+             "nw_core_batch_decode_ex", "nw_core_batch_raw_votes", "nw_core_messages_verify_ex",
+             "nw_core_batch_verify_async", "nw_core_messages_verify_async", "nw_core_agg_create",
+             "nw_core_agg_destroy", "nw_core_agg_set_header", "nw_core_agg_advance_gc", "nw_core_agg_state",
+             "nw_core_agg_apply", "nw_core_agg_refs"}
 
 
 def _load() -> ctypes.CDLL:
@@ -138,6 +154,16 @@ def _load() -> ctypes.CDLL:
         "nw_core_batch_raw_votes": (S, [P]),
         "nw_core_messages_verify_ex": (I, [P, ctypes.POINTER(NwCommittee), ctypes.POINTER(NwCoreState), P, P, S, U32, P,
                                            U64, P, ctypes.POINTER(U64)]),
+        "nw_core_batch_verify_async": (I, [P, P, P, U64, P, ctypes.POINTER(U64), ctypes.POINTER(P)]),
+        "nw_core_messages_verify_async": (I, [P, ctypes.POINTER(NwCommittee), ctypes.POINTER(NwCoreState), P, P, S,
+                                              U32, P, U64, P, ctypes.POINTER(U64), ctypes.POINTER(P)]),
+        "nw_core_agg_create": (I, [ctypes.POINTER(NwCommittee), U64, ctypes.POINTER(P)]),
+        "nw_core_agg_destroy": (None, [P]),
+        "nw_core_agg_set_header": (I, [P, P, U64, P]),
+        "nw_core_agg_advance_gc": (I, [P, U64]),
+        "nw_core_agg_state": (I, [P, ctypes.POINTER(NwCoreState)]),
+        "nw_core_agg_apply": (I, [P, P, U64, P, ctypes.POINTER(ctypes.POINTER(NwCoreEvent)), ctypes.POINTER(S)]),
+        "nw_core_agg_refs": (I, [P, ctypes.POINTER(ctypes.POINTER(NwCoreRef)), ctypes.POINTER(S)]),
     }
     for name, (res, args) in sig.items():
         if name in _OPTIONAL and not hasattr(lib, name):
@@ -570,6 +596,138 @@ class Engine:
                                                    _buf(bytes(zseed)), cert_base, out, ctypes.byref(used)),
                        "nw_core_messages_verify")
         return list(out[:n]), used.value
+
+    def core_batch_submit(self, batch: "CoreFrameBatch", zseed: bytes, cert_base: int = 0) -> "CoreJob":
+        """nw_core_batch_verify_async: enqueue the checks of a decoded batch and return at once.
+        ``job.certs_used`` is known on return; the batch may be closed before the job is waited for."""
+        return CoreJob(self, zseed, cert_base, batch=batch)
+
+    def core_messages_submit(self, committee: "CommitteeABI", state: Optional[NwCoreState], frames, zseed: bytes,
+                             cert_base: int = 0, device_votes: bool = False) -> "CoreJob":
+        """nw_core_messages_verify_async: decode + submit + free in one ABI call."""
+        return CoreJob(self, zseed, cert_base, frames=frames, committee=committee, state=state,
+                       flags=CORE_DEVICE_VOTES if device_votes else 0)
+
+
+class CoreJob:
+    """One nw_core_batch_verify_async (or nw_core_messages_verify_async) submission in flight.
+    ``done()`` polls; ``wait()`` returns the NW_DAG_* verdicts (waits exactly once).  ``engine`` may be
+    None for a batch the host decided completely.  ``verdicts`` is the int32 array the library fills:
+    CoreAgg.apply takes it as it is."""
+
+    def __init__(self, engine: Optional[Engine], zseed: bytes, cert_base: int = 0, batch: "CoreFrameBatch" = None,
+                 frames=None, committee: "CommitteeABI" = None, state: Optional[NwCoreState] = None, flags: int = 0):
+        self._engine = engine
+        ctx = engine.handle if engine is not None else None
+        used = ctypes.c_uint64(0)
+        self._job = ctypes.c_void_p()
+        if batch is not None:
+            self.n = len(batch)
+            self.verdicts = (ctypes.c_int32 * max(self.n, 1))()
+            rc = LIB.nw_core_batch_verify_async(ctx, batch.handle, _buf(bytes(zseed)), cert_base, self.verdicts,
+                                                ctypes.byref(used), ctypes.byref(self._job))
+            what = "nw_core_batch_verify_async"
+        else:
+            frames = [bytes(f) for f in frames]
+            self.n = n = len(frames)
+            ptrs = (ctypes.c_char_p * max(n, 1))(*frames)
+            lens = (ctypes.c_size_t * max(n, 1))(*[len(f) for f in frames])
+            self.verdicts = (ctypes.c_int32 * max(n, 1))()
+            st = ctypes.byref(state) if state is not None else None
+            rc = LIB.nw_core_messages_verify_async(ctx, ctypes.byref(committee.struct), st, ptrs, lens, n, flags,
+                                                   _buf(bytes(zseed)), cert_base, self.verdicts, ctypes.byref(used),
+                                                   ctypes.byref(self._job))
+            what = "nw_core_messages_verify_async"
+        self.rc = rc
+        if rc != NW_OK:
+            if engine is not None:
+                engine.check(rc, what)
+            raise DeviceError("%s failed (rc=%d)" % (what, rc))
+        self.certs_used = used.value
+
+    def done(self) -> bool:
+        if not self._job:
+            return True
+        rc = LIB.nw_job_done(self._job)
+        if rc < 0 or rc > 1:
+            raise DeviceError("nw_job_done failed (rc=%d)" % rc)
+        return rc == 1
+
+    def wait(self) -> list:
+        if self._job:
+            job, self._job = self._job, ctypes.c_void_p()
+            rc = LIB.nw_job_wait(job)
+            if rc != NW_OK:
+                raise DeviceError("nw_job_wait failed (rc=%d): %s" % (rc, (LIB.nw_last_error(None) or b"").decode()))
+        return list(self.verdicts[:self.n])
+
+    def __del__(self):
+        try:
+            if self._job:
+                LIB.nw_job_wait(self._job)   # a job must be waited for exactly once
+        except Exception:
+            pass
+
+
+class CoreAgg:
+    """nw_core_agg: the native votes / certificates aggregators and the apply-time state checks of
+    Core (host only).  ``apply`` returns (final verdicts, events); an event is (kind, round, tag, at,
+    refs) with refs a list of (tag, index, assembled)."""
+
+    def __init__(self, committee: "CommitteeABI", gc_depth: int):
+        self._h = ctypes.c_void_p()
+        self._committee = committee
+        rc = LIB.nw_core_agg_create(ctypes.byref(committee.struct), gc_depth, ctypes.byref(self._h))
+        if rc != NW_OK:
+            raise DeviceError("nw_core_agg_create failed (rc=%d)" % rc)
+
+    def set_header(self, header_id: bytes, round_: int, author: bytes) -> None:
+        rc = LIB.nw_core_agg_set_header(self._h, bytes(header_id), round_, bytes(author))
+        if rc != NW_OK:
+            raise DeviceError("nw_core_agg_set_header failed (rc=%d)" % rc)
+
+    def advance_gc(self, consensus_round: int) -> None:
+        rc = LIB.nw_core_agg_advance_gc(self._h, consensus_round)
+        if rc != NW_OK:
+            raise DeviceError("nw_core_agg_advance_gc failed (rc=%d)" % rc)
+
+    def state(self) -> dict:
+        st = NwCoreState()
+        rc = LIB.nw_core_agg_state(self._h, ctypes.byref(st))
+        if rc != NW_OK:
+            raise DeviceError("nw_core_agg_state failed (rc=%d)" % rc)
+        return {"gc_round": st.gc_round, "id": bytes(st.id), "round": st.round, "author": bytes(st.author)}
+
+    def apply(self, batch: "CoreFrameBatch", tag: int, verdicts):
+        n = len(batch)
+        if not isinstance(verdicts, ctypes.Array):
+            verdicts = (ctypes.c_int32 * max(n, 1))(*verdicts)
+        ev = ctypes.POINTER(NwCoreEvent)()
+        nev = ctypes.c_size_t(0)
+        rc = LIB.nw_core_agg_apply(self._h, batch.handle, tag, verdicts, ctypes.byref(ev), ctypes.byref(nev))
+        if rc != NW_OK:
+            raise DeviceError("nw_core_agg_apply failed (rc=%d)" % rc)
+        refs = ctypes.POINTER(NwCoreRef)()
+        nrefs = ctypes.c_size_t(0)
+        LIB.nw_core_agg_refs(self._h, ctypes.byref(refs), ctypes.byref(nrefs))
+        events = []
+        for k in range(nev.value):
+            e = ev[k]
+            assert e.first + e.count <= nrefs.value
+            events.append((e.kind, e.round, e.tag, e.at,
+                           [(refs[j].tag, refs[j].index, refs[j].assembled) for j in range(e.first, e.first + e.count)]))
+        return list(verdicts[:n]), events
+
+    def close(self):
+        if self._h:
+            LIB.nw_core_agg_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class DigestJob:

@@ -24,6 +24,7 @@ and verdict comes from libnwcrypto.
 from __future__ import annotations
 
 import os
+import struct
 from typing import Callable, Dict, Iterable, List, Optional, Sequence, Tuple
 
 from . import _lib
@@ -232,7 +233,12 @@ class CoreBatcher:
     signature: ``check_messages``) already run on the GPU from a worker thread (ctypes releases the
     GIL during the library calls).  The state-dependent checks (TooOld against gc_round,
     UnexpectedVote against the current header) are evaluated when a batch is applied, against the
-    state at that moment, so the results equal ``submit`` called batch after batch."""
+    state at that moment, so the results equal ``submit`` called batch after batch.
+
+    ``submit_frames_native(frames)`` and ``pipeline_frames(batches)`` are the same two on wire frames
+    with nothing but the hand-off in Python: asynchronous native jobs (nw_core_batch_verify_async),
+    then the native aggregators (nw_core_agg_apply) for the state checks, the votes and the
+    certificates."""
 
     def __init__(self, committee: Committee, engine=None, gc_depth: int = 50, device_votes: bool = False):
         self.committee = committee
@@ -250,6 +256,9 @@ class CoreBatcher:
         """process_own_header (core.rs:117-120): a fresh votes aggregator for our new header."""
         self.current_header = header
         self.votes_aggregator = VotesAggregator()
+        if self._agg is not None:
+            self._agg.set_header(header.id, header.round, header.author)
+            self._held_votes.clear()
 
     def _process_certificate(self, cert: Certificate, parents_out: list) -> None:
         agg = self.certificates_aggregators.setdefault(cert.round(), CertificatesAggregator())
@@ -351,3 +360,132 @@ class CoreBatcher:
             self.gc_round = consensus_round - self.gc_depth
             self.certificates_aggregators = {r: a for r, a in self.certificates_aggregators.items()
                                              if r >= self.gc_round}
+        if self._agg is not None:
+            self._agg.advance_gc(consensus_round)
+            for key in [k for k, c in self._held_certs.items() if self._held_round(c) < self.gc_round]:
+                del self._held_certs[key]
+
+    # ---- the native apply path (nw_core_agg) ---------------------------------------
+    # A batcher that uses submit_frames_native / pipeline_frames keeps its votes and certificates in
+    # ONE native aggregator (created on first use from the state at that moment) instead of the Python
+    # aggregators above; the two sets of methods are not to be mixed on one batcher.  The aggregator
+    # names a vote or a certificate by (tag, index) of its frame: the messages it may still name are
+    # held here, decoded, until an event hands them on or a state change drops them.
+    _agg: Optional["_lib.CoreAgg"] = None
+
+    def _native_agg(self) -> "_lib.CoreAgg":
+        if self._agg is None:
+            self._agg = _lib.CoreAgg(committee_abi(self.committee), self.gc_depth)
+            h = self.current_header
+            self._agg.set_header(h.id, h.round, h.author)
+            if self.gc_round:
+                self._agg.advance_gc(self.gc_round + self.gc_depth)
+            self._tag = 0
+            self._held_votes: Dict[Tuple[int, int], bytes] = {}
+            self._held_certs: Dict[tuple, object] = {}   # (tag, index): frame; (tag, index, "assembled"): Certificate
+        return self._agg
+
+    def _decode_native(self, frames: Sequence[bytes]) -> "_lib.CoreFrameBatch":
+        return _lib.CoreFrameBatch(committee_abi(self.committee), frames, None, device_votes=self.device_votes)
+
+    def _apply_native(self, frames: Sequence[bytes], batch: "_lib.CoreFrameBatch", verdicts):
+        """nw_core_agg_apply on a checked batch, and its events turned into ``_apply``'s results.
+        The frames of accepted votes and certificates are held as bytes; decode_primary_message runs
+        only on the frames an event refers to."""
+        agg = self._native_agg()
+        tag = self._tag
+        self._tag += 1
+        codes, events = agg.apply(batch, tag, verdicts)
+        for i, c in enumerate(codes):
+            if c == _lib.DAG_OK and len(frames[i]) >= 4:
+                variant = frames[i][0]            # PrimaryMessage variant: 1 Vote, 2 Certificate (little-endian u32)
+                if variant == 1:
+                    self._held_votes[(tag, i)] = frames[i]
+                elif variant == 2:
+                    self._held_certs[(tag, i)] = frames[i]
+        assembled: List[Certificate] = []
+        parents: List[Tuple[List[Certificate], int]] = []
+        for kind, round_, etag, at, refs in events:
+            if kind == _lib.CORE_EVENT_CERT_ASSEMBLED:
+                votes = [decode_primary_message(self._held_votes[(t, i)]) for t, i, _ in refs]
+                cert = Certificate(self.current_header, [(v.author, v.signature) for v in votes])
+                assembled.append(cert)
+                self._held_certs[(etag, at, "assembled")] = cert
+            else:
+                got = [self._held_certs.pop((t, i, "assembled") if a else (t, i)) for t, i, a in refs]
+                parents.append(([c if isinstance(c, Certificate) else decode_primary_message(c) for c in got], round_))
+        return _errors(codes), assembled, parents
+
+    @staticmethod
+    def _held_round(c) -> int:
+        """Round of a held certificate: an assembled one, or a frame (variant, author string, round)."""
+        if isinstance(c, Certificate):
+            return c.round()
+        (klen,) = struct.unpack_from("<Q", c, 4)
+        return struct.unpack_from("<Q", c, 12 + klen)[0]
+
+    def submit_frames_native(self, frames: Sequence[bytes], zseed: Optional[bytes] = None):
+        """``submit_frames`` with nothing but the hand-off in Python: native decode (NULL state),
+        nw_core_batch_verify_async + nw_job_wait, then nw_core_agg_apply for the state checks and the
+        aggregators.  Returns what ``submit_frames`` returns."""
+        frames = [bytes(f) for f in frames]
+        batch = self._decode_native(frames)
+        job = self.engine.core_batch_submit(batch, zseed if zseed is not None else os.urandom(32), self.cert_base)
+        self.cert_base += job.certs_used
+        job.wait()
+        try:
+            return self._apply_native(frames, batch, job.verdicts)
+        finally:
+            batch.close()
+
+    def pipeline_frames(self, batches: Iterable[Sequence[bytes]], zseed: Optional[bytes] = None,
+                        before_apply: Optional[Callable[[int, "CoreBatcher"], None]] = None, depth: int = 2):
+        """The native counterpart of ``pipeline``, on one thread: up to ``depth`` batches are in
+        flight on the GPU as asynchronous jobs (``cert_base`` advances at submit), and each is applied
+        in submission order after its nw_job_wait, by the native aggregator.  ``before_apply(k, self)``
+        runs just before batch k is applied; its set_current_header / advance_gc reach the native
+        aggregator too.  Yields ``submit_frames``'s result for each batch."""
+        from collections import deque
+        it = iter(batches)
+        trace = self.trace
+        flying = deque()
+        self._native_agg()
+        submitted = 0
+
+        def submit_next():
+            nonlocal submitted
+            frames = next(it, None)
+            if frames is None:
+                return
+            frames = [bytes(f) for f in frames]
+            batch = self._decode_native(frames)
+            job = self.engine.core_batch_submit(batch, zseed if zseed is not None else os.urandom(32),
+                                                self.cert_base)
+            self.cert_base += job.certs_used
+            flying.append((submitted, frames, batch, job))
+            if trace is not None:
+                trace.append(("submitted", submitted))
+            submitted += 1
+
+        try:
+            while len(flying) < max(1, depth):
+                n0 = len(flying)
+                submit_next()
+                if len(flying) == n0:
+                    break
+            while flying:
+                k, frames, batch, job = flying[0]
+                job.wait()
+                submit_next()   # keeps ``depth`` jobs in flight under the apply below
+                if before_apply is not None:
+                    before_apply(k, self)
+                res = self._apply_native(frames, batch, job.verdicts)
+                flying.popleft()
+                batch.close()
+                if trace is not None:
+                    trace.append(("apply_done", k))
+                yield res
+        finally:
+            for _, _, batch, job in flying:   # abandoned mid-way: every job is still waited for once
+                job.wait()
+                batch.close()

@@ -11,21 +11,17 @@
 
 using namespace nw;
 
-// An asynchronous host-buffer call in flight (nw_sha512_many_async): its workspace lease, the
-// caller's output and where the digests land in the workspace's pinned buffer.
-struct nw_job {
-    std::unique_ptr<Lease> lease;
-    uint8_t* out = nullptr;
-    size_t n = 0;
-    size_t o_out = 0;
-    std::atomic<int>* inflight = nullptr;   // the context's async job count (released with the job)
-    ~nw_job() {
-        lease.reset();
-        if (inflight) inflight->fetch_sub(1);
-    }
-};
-
 namespace nw {
+
+int claim_job_slot(nw_ctx* ctx, nw_job* j, const char* who) {
+    if (ctx->async_jobs.fetch_add(1) >= kMaxAsyncJobs) {
+        ctx->async_jobs.fetch_sub(1);
+        set_error(ctx, std::string(who) + ": too many unwaited jobs (limit 32; wait for one first)");
+        return NW_ERR_NOMEM;
+    }
+    j->inflight = &ctx->async_jobs;
+    return NW_OK;
+}
 
 int enqueue_certs(nw_ctx* ctx, Workspace* ws, const CertCall& c, const CertPlan& p, const CertScratch& s,
                   hipStream_t st) {
@@ -793,12 +789,7 @@ int nw_sha512_many_async(nw_ctx* ctx, const uint8_t* const* msg, const size_t* l
         return NW_OK;
     }
     NW_TRY(hipSetDevice(ctx->device), "hipSetDevice");
-    if (ctx->async_jobs.fetch_add(1) >= kMaxAsyncJobs) {
-        ctx->async_jobs.fetch_sub(1);
-        set_error(ctx, "nw_sha512_many_async: too many unwaited jobs (limit 32; wait for one first)");
-        return NW_ERR_NOMEM;
-    }
-    j->inflight = &ctx->async_jobs;
+    NW_RC(claim_job_slot(ctx, j.get(), "nw_sha512_many_async"));
     const DigestPack pack = digest_pack(len, n);
     const DigestLayout l(n, pack.total, true);
     j->lease = std::make_unique<Lease>(ctx, nullptr, l.bytes());
@@ -838,7 +829,7 @@ int nw_job_wait(nw_job* job) {
         set_error(nullptr, std::string("nw_job_wait: ") + hipGetErrorString(e));
         return NW_ERR_DEVICE;   // the lease synchronizes its stream on release
     }
-    std::memcpy(own->out, ws->h_io.bytes() + own->o_out, own->n * 64);
+    std::memcpy(own->out, ws->h_io.bytes() + own->o_out, own->n * own->item);
     own->lease->synced();
     return NW_OK;
 }

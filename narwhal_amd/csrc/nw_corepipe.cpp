@@ -12,7 +12,8 @@
 //   5. certificate pass         enqueue_certs, batch_mode 1: the votes of the certificates that enter
 //                               the batch step -> one verdict byte per certificate
 //   6. k_core_verdict           id check + fold -> n int32 verdicts
-//   7. one D2H copy of the verdicts, then one stream synchronization
+//   7. one D2H copy of the verdicts, then one stream synchronization (nw_core_batch_verify) or the
+//      workspace's completion event (nw_core_batch_verify_async: nw_job_wait waits for it)
 // Nothing the host does in the three-submission form (nw_cert_batch_verify) between its submissions
 // is needed for the next kernel to start: the digest is the signature's message, so it is read from
 // device memory, and the id comparison and the error precedence only decide the final verdict.
@@ -24,34 +25,54 @@
 
 using namespace nw;
 
-extern "C" {
+// The two entry points (nw_core_batch_verify and nw_core_batch_verify_async) are the same three
+// parts; they differ in who owns the workspace lease and in when the verdicts are copied out:
+//   core_open      argument checks, *certs_used, and a batch the host decided completely
+//   core_keys      the committee's keys into the key cache -> their slots
+//   core_enqueue   steps 1-6 and the D2H of step 7 on the leased workspace's stream
+//   completion     synchronous: HostCall::finish, then the copy out of the pinned buffer;
+//                  asynchronous: Lease::finish (the event), and nw_job_wait does both later.
+namespace {
 
-int nw_core_batch_verify(nw_ctx* ctx, const nw_core_batch* b, const uint8_t zseed[32], uint64_t cert_base,
-                         int32_t* verdict, uint64_t* certs_used) {
+// NW_OK with *decided set: the host decided every message, verdict is filled, nothing to launch.
+int core_open(nw_ctx* ctx, const nw_core_batch* b, const uint8_t* zseed, int32_t* verdict, uint64_t* certs_used,
+              bool* decided) {
+    *decided = false;
     if (!b || (!verdict && !b->msgs.empty())) return NW_ERR_ARG;
     if (!zseed) {
         set_error(ctx, "zseed is NULL: batch coefficients need a fresh 32-byte CSPRNG seed per call");
         return NW_ERR_ARG;
     }
-    const size_t n = b->msgs.size(), D = b->dig_off.size(), H = b->ids.size() / 32, S = b->smember.size(),
-                 C = b->cnv.size(), V = b->cert_votes;
+    const size_t n = b->msgs.size(), D = b->dig_off.size(), S = b->smember.size(), C = b->cnv.size(),
+                 V = b->cert_votes;
     if (certs_used) *certs_used = C;
     if (b->pending == 0) {   // the host decided every message: nothing to launch, no device needed
         for (size_t i = 0; i < n; ++i) verdict[i] = b->desc[i].status;
+        *decided = true;
         return NW_OK;
     }
     if (!ctx) return NW_ERR_ARG;
     if (n > 0xFFFFFFF0u || D > 0xFFFFFFF0u || S + C > 0xFFFFFFF0u || V > 0xFFFFFFF0u) return NW_ERR_ARG;
-    // Committee keys go to the key cache first (nw_committee_load takes the key lock exclusively, so
-    // before this call takes it shared); cached keys keep their slots.
-    std::vector<uint32_t> slot(b->names.size());
-    if ((S || C) && !b->names.empty())
+    return NW_OK;
+}
+
+// Committee keys go to the key cache first (nw_committee_load takes the key lock exclusively, so
+// before the call takes it shared); cached keys keep their slots.
+int core_keys(nw_ctx* ctx, const nw_core_batch* b, std::vector<uint32_t>& slot) {
+    slot.assign(b->names.size(), 0);
+    if ((!b->smember.empty() || !b->cnv.empty()) && !b->names.empty())
         NW_RC(nw_committee_load(ctx, reinterpret_cast<const uint8_t(*)[32]>(b->names.data()), b->stakes.data(),
                                 b->names.size(), slot.data()));
-    HostCall call(ctx);
-    NW_RC(call.begin());
-    Workspace* ws = call.ws;
-    hipStream_t st = call.st;
+    return NW_OK;
+}
+
+// Shared key lock held, ws leased and bound to st (its own stream).  Everything of b and zseed that
+// the device needs is copied here, into the pinned block or into kernel arguments: both may be freed
+// when this returns.  The verdicts end up in the first n * 4 bytes of ws->h_io once st has drained.
+int core_enqueue(nw_ctx* ctx, Workspace* ws, hipStream_t st, const nw_core_batch* b, const std::vector<uint32_t>& slot,
+                 const uint8_t* zseed, uint64_t cert_base) {
+    const size_t n = b->msgs.size(), D = b->dig_off.size(), H = b->ids.size() / 32, S = b->smember.size(),
+                 C = b->cnv.size(), V = b->cert_votes;
     // raw certificates: their vote sections and the device committee index ride in the same block
     const size_t K = b->raw_certs ? b->names.size() : 0, raw_bytes = (b->raw.size() + 15) & ~(size_t)15;
     const CoreLayout l(n, D, b->pre.size(), H, S, C, V, raw_bytes, K);
@@ -211,10 +232,68 @@ int nw_core_batch_verify(nw_ctx* ctx, const nw_core_batch* b, const uint8_t zsee
     vp.vote_err = vplan.grid ? reinterpret_cast<const int32_t*>(d_work + l.verr) : nullptr;
     vp.verdict = reinterpret_cast<int32_t*>(d_out + l.verdict);
     NW_TRY(launch_core_verdict(vp, st), "k_core_verdict");
-    // 7. the H2D above has completed in stream order before this copy overwrites the staging buffer
+    // 7. The verdicts land on the front of the staging buffer, over inputs staged there.  Stream order
+    // makes that safe, for the synchronous call and for a job alike: the one H2D of step 1 is the only
+    // reader of h on the device's side and it has completed before this copy starts; every later step
+    // reads device memory only; and the host reads h no more after staging.  The lease keeps h from
+    // any other call until the verdicts have been copied out of it.
     NW_TRY(hipMemcpyAsync(h, d_out + l.verdict, n * 4, hipMemcpyDeviceToHost, st), "D2H verdicts");
+    return NW_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nw_core_batch_verify(nw_ctx* ctx, const nw_core_batch* b, const uint8_t zseed[32], uint64_t cert_base,
+                         int32_t* verdict, uint64_t* certs_used) {
+    bool decided = false;
+    NW_RC(core_open(ctx, b, zseed, verdict, certs_used, &decided));
+    if (decided) return NW_OK;
+    std::vector<uint32_t> slot;
+    NW_RC(core_keys(ctx, b, slot));
+    HostCall call(ctx);
+    NW_RC(call.begin());
+    NW_RC(core_enqueue(ctx, call.ws, call.st, b, slot, zseed, cert_base));
     NW_RC(call.finish());
-    std::memcpy(verdict, h, n * 4);
+    std::memcpy(verdict, call.ws->h_io.bytes(), b->msgs.size() * 4);
+    return NW_OK;
+}
+
+// The asynchronous form (the reference's Core blocks on each message's check in its one task,
+// primary/src/core.rs:351-389; a caller of this one goes on receiving while the batch is checked).
+// The job keeps the workspace lease from here to nw_job_wait.  Unlike a digest job it reads the key
+// tables, so the lease is taken and the work enqueued under the shared key lock, as HostCall does,
+// and the event is recorded through Lease::finish: the workspace is pending, and a committee load
+// that changes the cache (exclusive lock, drain_all) waits for it.  The lock itself is dropped on
+// return.  A job abandoned on an error drains its stream when its lease is released.
+int nw_core_batch_verify_async(nw_ctx* ctx, const nw_core_batch* b, const uint8_t zseed[32], uint64_t cert_base,
+                               int32_t* verdict, uint64_t* certs_used, nw_job** job) {
+    if (!job) return NW_ERR_ARG;
+    *job = nullptr;
+    bool decided = false;
+    NW_RC(core_open(ctx, b, zseed, verdict, certs_used, &decided));
+    auto j = std::make_unique<nw_job>();
+    j->item = 4;
+    if (decided) {   // complete already: no lease, no job slot, nothing for nw_job_wait to copy
+        *job = j.release();
+        return NW_OK;
+    }
+    j->out = reinterpret_cast<uint8_t*>(verdict);
+    j->n = b->msgs.size();
+    NW_RC(claim_job_slot(ctx, j.get(), "nw_core_batch_verify_async"));   // before anything is loaded or enqueued
+    std::vector<uint32_t> slot;
+    NW_RC(core_keys(ctx, b, slot));
+    NW_TRY(hipSetDevice(ctx->device), "hipSetDevice");
+    {
+        std::shared_lock<std::shared_mutex> keys(ctx->keys_mu);
+        j->lease = std::make_unique<Lease>(ctx);
+        NW_RC(j->lease->open(true));
+        Workspace* ws = j->lease->ws();
+        NW_RC(core_enqueue(ctx, ws, ws->stream, b, slot, zseed, cert_base));
+        NW_TRY(j->lease->finish(), "hipEventRecord");
+    }
+    *job = j.release();
     return NW_OK;
 }
 
@@ -232,6 +311,20 @@ int nw_core_messages_verify_ex(nw_ctx* ctx, const nw_committee* cm, const nw_cor
     if (rc != NW_OK) return rc;
     rc = nw_core_batch_verify(ctx, b, zseed, cert_base, verdict, certs_used);
     nw_core_batch_free(b);
+    return rc;
+}
+
+int nw_core_messages_verify_async(nw_ctx* ctx, const nw_committee* cm, const nw_core_state* state,
+                                  const uint8_t* const* frame, const size_t* len, size_t n, uint32_t flags,
+                                  const uint8_t zseed[32], uint64_t cert_base, int32_t* verdict, uint64_t* certs_used,
+                                  nw_job** job) {
+    if (!job) return NW_ERR_ARG;
+    *job = nullptr;
+    nw_core_batch* b = nullptr;
+    int rc = nw_core_batch_decode_ex(cm, state, frame, len, n, flags, &b);
+    if (rc != NW_OK) return rc;
+    rc = nw_core_batch_verify_async(ctx, b, zseed, cert_base, verdict, certs_used, job);
+    nw_core_batch_free(b);   // everything the job needs is staged
     return rc;
 }
 

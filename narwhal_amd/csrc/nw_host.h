@@ -16,6 +16,9 @@
 //     ``_dev`` calls run on the caller's stream and leave the workspace "pending" until its event
 //     completes — the next lease of that workspace waits on the event (stream order, or a host wait
 //     before a block is reallocated), so device memory is never reused while a kernel may still read it.
+//     Asynchronous jobs (nw_job) keep their lease from submit to nw_job_wait: a digest job without the
+//     key lock and without marking the workspace pending, a Core job with the lock held while it
+//     enqueues and the workspace pending, so a committee load that changes the cache waits for it.
 //
 // A workspace owns two device blocks, and every call lays both out afresh (nw_host_plan.h):
 //   io       inputs at the SAME offsets as in the pinned block h_io they are staged in, outputs behind them;
@@ -156,9 +159,9 @@ struct Workspace {
 };
 
 constexpr size_t kMaxWorkspaces = 64;   // one per concurrently calling thread (the worker's 64)
-// Asynchronous digest jobs hold a workspace from submit to nw_job_wait; past this many unwaited jobs
-// a submit fails at once (NW_ERR_NOMEM) instead of blocking on a pool that only those jobs' own
-// waits could refill.  The other half of the pool stays for synchronous calls.
+// Asynchronous jobs (digest and Core jobs alike) hold a workspace from submit to nw_job_wait; past
+// this many unwaited jobs a submit fails at once (NW_ERR_NOMEM) instead of blocking on a pool that
+// only those jobs' own waits could refill.  The other half of the pool stays for synchronous calls.
 constexpr int kMaxAsyncJobs = (int)kMaxWorkspaces / 2;
 
 }  // namespace nw
@@ -192,7 +195,7 @@ struct nw_ctx {
     std::condition_variable pool_cv;
     std::vector<std::unique_ptr<nw::Workspace>> pool;
     std::vector<nw::Workspace*> free_ws;
-    std::atomic<int> async_jobs{0};   // unwaited nw_sha512_many_async jobs (<= kMaxAsyncJobs)
+    std::atomic<int> async_jobs{0};   // unwaited asynchronous jobs of both kinds (<= kMaxAsyncJobs)
     // measurement: (start, stop) event pairs around k_verify launches
     std::mutex prof_mu;
     bool prof_on = false;
@@ -279,6 +282,30 @@ private:
     std::shared_lock<std::shared_mutex> keys_;   // released after the lease
     std::optional<Lease> lease_;
 };
+
+}  // namespace nw
+
+// An asynchronous host-buffer call in flight: its workspace lease, the caller's output and where the
+// result lands in the workspace's pinned buffer.  Two kinds, told apart only by what nw_job_wait
+// copies out: n x 64 digest bytes (nw_sha512_many_async) or n x 4 verdict bytes
+// (nw_core_batch_verify_async).  A job without a lease was complete when it was made.
+struct nw_job {
+    std::unique_ptr<nw::Lease> lease;
+    uint8_t* out = nullptr;
+    size_t n = 0;
+    size_t item = 64;    // bytes per result: 64 (digest) or 4 (verdict)
+    size_t o_out = 0;
+    std::atomic<int>* inflight = nullptr;   // the context's async job count (released with the job)
+    ~nw_job() {
+        lease.reset();
+        if (inflight) inflight->fetch_sub(1);
+    }
+};
+
+namespace nw {
+
+// Take one of the context's kMaxAsyncJobs job slots for j, or fail at once (NW_ERR_NOMEM, error text set).
+int claim_job_slot(nw_ctx* ctx, nw_job* j, const char* who);
 
 // One run of the certificate pipeline (nw_api.cpp).  Every pointer is device memory except zseed;
 // fields left unset are null / zero.

@@ -114,10 +114,16 @@ int HostCall::finish() {
     return NW_OK;
 }
 
-// Every verification lease is taken under the shared key lock, so none is live here.  Asynchronous
-// digest jobs (nw_sha512_many_async) hold their lease WITHOUT the key lock, so one may be live: it
-// reads no key table, its completion event is only re-recorded by its own submit, and every write
-// of ``pending`` (Lease::finish / synced / release) happens under pool_mu, as these reads do.
+// Every synchronous verification lease is taken and released under the shared key lock, so none is
+// live here.  Two kinds of asynchronous job keep a lease past the lock, so theirs may be live:
+//   * a digest job (nw_sha512_many_async) holds its lease WITHOUT the key lock and does not mark the
+//     workspace pending: it reads no key table, so nothing here waits for it;
+//   * a Core job (nw_core_batch_verify_async) reads the key tables.  It takes its lease and enqueues
+//     under the shared key lock and records its event through Lease::finish, so its workspace is
+//     pending although leased: the loop below walks the whole pool, leased workspaces included, and
+//     waits for it.  Its lease stays out until nw_job_wait, which finds the event complete.
+// A job's completion event is only re-recorded by its own submit, and every write of ``pending``
+// (Lease::finish / synced / release) happens under pool_mu, as these reads do.
 int drain_all(nw_ctx* ctx) {
     std::lock_guard<std::mutex> g(ctx->pool_mu);
     for (auto& w : ctx->pool)
