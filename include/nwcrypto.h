@@ -240,8 +240,9 @@ int nw_sha512_many_dev(nw_ctx* ctx, const uint8_t* d_base, const uint64_t* d_off
  * A job holds one of the context's 64 call workspaces until it is waited for; at most 32 jobs may be
  * unwaited at once (the rest of the pool stays for synchronous calls): a 33rd submit returns
  * NW_ERR_NOMEM at once rather than blocking.  nw_job_done and nw_job_wait serve the Core jobs of
- * nw_core_batch_verify_async as well (nw_job_wait then fills n x 4 verdict bytes), and the limit of
- * 32 counts the jobs of both kinds together. */
+ * nw_core_batch_verify_async as well (nw_job_wait then fills n x 4 verdict bytes) and the worker
+ * windows of nw_worker_window_async (n x 88 bytes), and the limit of 32 counts the jobs of all kinds
+ * together. */
 typedef struct nw_job nw_job;
 int nw_sha512_many_async(nw_ctx* ctx, const uint8_t* const* msg, const size_t* len, size_t n,
                          uint8_t (*out)[64], nw_job** job);
@@ -530,6 +531,75 @@ int nw_core_agg_state(const nw_core_agg* agg, nw_core_state* out);
 int nw_core_agg_apply(nw_core_agg* agg, const nw_core_batch* batch, uint64_t tag, int32_t* verdict,
                       const nw_core_event** events, size_t* n_events);
 int nw_core_agg_refs(const nw_core_agg* agg, const nw_core_ref** refs, size_t* n);
+
+/* ---- worker windows (worker/src/processor.rs:63-81) ---------------------------------------------
+ * What the reference's Processor does per received batch: the digest (:65) and, with
+ * enable_verification, the simulated signature load (:67-81), for a whole window of serialized
+ * batches in ONE asynchronous job, against a signature set that stays in HBM from spawn.
+ *
+ * nw_sigset is Processor::spawn's fixed load (:46-58): n (message, key-cache slot, signature)
+ * triples, uploaded once.  nw_sigset_create takes the key lock shared and rejects a slot outside the
+ * key cache (NW_ERR_ARG): load the keys first (nw_committee_load); slots stay valid across later
+ * loads because cached keys keep their slot.  The set owns its device allocation, outside the call
+ * workspaces.  nw_sigset_destroy only after every job that uses the set has been waited for. */
+typedef struct nw_sigset nw_sigset;
+int nw_sigset_create(nw_ctx* ctx, const uint8_t* const* msg, const size_t* len, const uint32_t* signer_slot,
+                     const uint8_t (*sig)[64], size_t n, nw_sigset** out);
+size_t nw_sigset_size(const nw_sigset* set);
+void nw_sigset_destroy(nw_sigset* set);
+
+#define NW_WORKER_OK 0             /* hashed; every chunk Ok (or nothing to verify) */
+#define NW_WORKER_VERIFY_FAILED 1  /* a chunk is Err: the reference's unwrap panics (processor.rs:78) */
+#define NW_WORKER_MALFORMED 2      /* bincode::deserialize fails: the reference panics (processor.rs:68) */
+
+typedef struct nw_worker_result {   /* 88 bytes */
+    uint8_t digest[64];   /* Sha512::digest(&batch) (:65); the reference keeps [..32]; always filled */
+    int64_t n_tx;         /* WorkerMessage::Batch: its transactions; -1: BatchRequest, malformed, or not parsed */
+    uint64_t chunk_ok;    /* bit c = verify_batch verdict of chunk c (:75-79); all ones when nothing was verified */
+    uint32_t verified;    /* min(set size, n_tx) (:70); 0 when nothing was verified */
+    int32_t status;       /* NW_WORKER_* */
+} nw_worker_result;
+
+/* Host only, no context, no GPU: what bincode::deserialize::<WorkerMessage> decides about one frame
+ * (processor.rs:68-69; worker/src/worker.rs:37-40).  bincode 1.3, fixint, little endian: u32 variant;
+ * Batch (0) = u64 count, then each transaction as u64 length + bytes; BatchRequest (1) = u64 count,
+ * that many 32-byte digests, then the requestor's key as its base64 string (u64 length + bytes,
+ * crypto/src/lib.rs:94-112; at least 32 decoded bytes).  Trailing bytes after a well-formed message
+ * are accepted, as bincode::deserialize accepts them.  NW_OK with *n_tx = the transaction count
+ * (Batch) or -1 (BatchRequest: ``if let WorkerMessage::Batch`` does not verify it); NW_ERR_ARG for a
+ * malformed frame (the reference's unwrap panics) or a NULL argument.  Counts and lengths up to
+ * 2^64 - 1 neither wrap a position nor allocate. */
+int nw_worker_frame_count(const uint8_t* frame, size_t len, int64_t* n_tx);
+
+/* One window of nb serialized batches, frame[i] (len[i] bytes), as one asynchronous job: one upload,
+ * the digests, the verify load and one download of out[nb].  The frames must stay valid until
+ * nw_job_wait, as for nw_sha512_many_async; out (nb x sizeof(nw_worker_result)) is filled by
+ * nw_job_wait; nw_job_done polls.  The job counts against the limit of 32 unwaited jobs.
+ *
+ * set == NULL is enable_verification == false: frames are hashed and not parsed; every result is
+ * NW_WORKER_OK with n_tx -1, verified 0 and chunk_ok all ones; zseed may be NULL.
+ *
+ * With a set every frame is parsed on the host by the rule of nw_worker_frame_count.  The j-th
+ * VERIFYING frame of the call is the j-th frame, in arrival order, that parsed as a Batch (one with
+ * 0 transactions included).  It verifies the set's first count = min(set size, n_tx) signatures
+ * (:70) as 64 chunks, chunk c = [count*c/64, min(count, count*(c+1)/64)) (:76-77, in 64-bit), chunk
+ * c with NW-Z v1 batch index batch_base + 64 j + c: chunk_ok bit c is what nw_verify_batches returns
+ * for those 64 ranges over the same triples with batch_base + 64 j.  An empty chunk is Ok.  A
+ * malformed frame (NW_WORKER_MALFORMED, n_tx -1) still gets its digest, because the reference hashes
+ * at :65 before it panics at :68; a BatchRequest is NW_WORKER_OK with n_tx -1; neither uses batch
+ * indices.  *batches_used (may be NULL) = 64 x (number of verifying frames), written before the
+ * call returns, so the next window can be submitted (batch_base + *batches_used) while this one is
+ * in flight.  zseed: 32 fresh CSPRNG bytes per call, as for every batch entry point.
+ *
+ * The job reads the key tables: an nw_committee_load that adds keys while it is in flight waits for
+ * it on the device, as for Core jobs.  NW_ERR_ARG: NULL ctx, out or job, NULL zseed with a set, a set
+ * of another context, nb or the window's virtual signature total (the sum of count) above 0xFFFFFFF0. */
+int nw_worker_window_async(nw_ctx* ctx, const nw_sigset* set, const uint8_t* const* frame, const size_t* len,
+                           size_t nb, const uint8_t zseed[32], uint64_t batch_base, nw_worker_result* out,
+                           uint64_t* batches_used, nw_job** job);
+/* The same, submit + wait: out is filled on return. */
+int nw_worker_window(nw_ctx* ctx, const nw_sigset* set, const uint8_t* const* frame, const size_t* len, size_t nb,
+                     const uint8_t zseed[32], uint64_t batch_base, nw_worker_result* out, uint64_t* batches_used);
 
 /* Library build identifier (gfx target, build date). */
 const char* nw_version(void);

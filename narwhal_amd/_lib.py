@@ -95,7 +95,11 @@ _OPTIONAL = {"nw_abi_version", "nw_profile_read_sigs", "nw_base_window", "nw_cer
              "nw_core_batch_decode_ex", "nw_core_batch_raw_votes", "nw_core_messages_verify_ex",
              "nw_core_batch_verify_async", "nw_core_messages_verify_async", "nw_core_agg_create",
              "nw_core_agg_destroy", "nw_core_agg_set_header", "nw_core_agg_advance_gc", "nw_core_agg_state",
-             "nw_core_agg_apply", "nw_core_agg_refs"}
+             "nw_core_agg_apply", "nw_core_agg_refs", "nw_sigset_create", "nw_sigset_size", "nw_sigset_destroy",
+             "nw_worker_frame_count", "nw_worker_window_async", "nw_worker_window"}
+
+WORKER_OK, WORKER_VERIFY_FAILED, WORKER_MALFORMED = 0, 1, 2   # NW_WORKER_* (nw_worker_result.status)
+WORKER_CHUNKS = 64                                            # verify_batch chunks per batch
 
 
 def _load() -> ctypes.CDLL:
@@ -164,6 +168,12 @@ def _load() -> ctypes.CDLL:
         "nw_core_agg_state": (I, [P, ctypes.POINTER(NwCoreState)]),
         "nw_core_agg_apply": (I, [P, P, U64, P, ctypes.POINTER(ctypes.POINTER(NwCoreEvent)), ctypes.POINTER(S)]),
         "nw_core_agg_refs": (I, [P, ctypes.POINTER(ctypes.POINTER(NwCoreRef)), ctypes.POINTER(S)]),
+        "nw_sigset_create": (I, [P, P, P, P, P, S, ctypes.POINTER(P)]),
+        "nw_sigset_size": (S, [P]),
+        "nw_sigset_destroy": (None, [P]),
+        "nw_worker_frame_count": (I, [P, S, ctypes.POINTER(ctypes.c_int64)]),
+        "nw_worker_window_async": (I, [P, P, P, P, S, P, U64, P, ctypes.POINTER(U64), ctypes.POINTER(P)]),
+        "nw_worker_window": (I, [P, P, P, P, S, P, U64, P, ctypes.POINTER(U64)]),
     }
     for name, (res, args) in sig.items():
         if name in _OPTIONAL and not hasattr(lib, name):
@@ -607,6 +617,121 @@ class Engine:
         """nw_core_messages_verify_async: decode + submit + free in one ABI call."""
         return CoreJob(self, zseed, cert_base, frames=frames, committee=committee, state=state,
                        flags=CORE_DEVICE_VOTES if device_votes else 0)
+
+    # -- worker windows (nw_worker_window_async) -------------------------------------------------
+    def sigset(self, msgs, signer_slots, sigs) -> "SigSet":
+        """nw_sigset_create: keep (message, key-cache slot, signature) triples resident in HBM."""
+        return SigSet(self, msgs, signer_slots, sigs)
+
+    def worker_window_submit(self, frames, sigset: Optional["SigSet"] = None, zseed: Optional[bytes] = None,
+                             batch_base: int = 0) -> "WorkerJob":
+        """nw_worker_window_async: the digests and the verify load of a window of serialized batches as
+        one job; returns at once.  ``sigset`` None: digests only (enable_verification == false)."""
+        return WorkerJob(self, frames, sigset, zseed, batch_base)
+
+
+def worker_result_dtype():
+    """nw_worker_result (88 bytes) as a numpy structured dtype."""
+    import numpy as np
+    return np.dtype([("digest", np.uint8, (64,)), ("n_tx", "<i8"), ("chunk_ok", "<u8"), ("verified", "<u4"),
+                     ("status", "<i4")])
+
+
+def worker_frame_count(frame) -> int:
+    """nw_worker_frame_count (host only, no GPU): transactions of a serialized ``WorkerMessage::Batch``,
+    -1 for a well-formed ``BatchRequest``; ValueError for a malformed frame, where the reference's
+    ``deserialize(..).unwrap()`` panics (worker/src/processor.rs:68)."""
+    frame = bytes(frame)
+    n_tx = ctypes.c_int64(0)
+    if LIB.nw_worker_frame_count(_buf(frame), len(frame), ctypes.byref(n_tx)) != NW_OK:
+        raise ValueError("WorkerMessage: malformed frame")
+    return n_tx.value
+
+
+class SigSet:
+    """nw_sigset: one Processor's (message, key-cache slot, signature) triples, resident in HBM from
+    spawn (worker/src/processor.rs:46-58).  msgs uint8[N, L], signer_slots uint32[N] (slots of keys
+    already loaded), sigs uint8[N, 64].  Close it only after every job that uses it has been waited for."""
+
+    def __init__(self, engine: "Engine", msgs, signer_slots, sigs):
+        import numpy as np
+        msgs = np.ascontiguousarray(msgs, dtype=np.uint8)
+        sigs = np.ascontiguousarray(sigs, dtype=np.uint8)
+        slots = np.ascontiguousarray(signer_slots, dtype=np.uint32)
+        n, ml = msgs.shape
+        if sigs.shape != (n, 64) or slots.shape != (n,):
+            raise ValueError("SigSet: msgs [N, L], signer_slots [N] and sigs [N, 64] must agree on N")
+        ptrs = (msgs.ctypes.data + np.arange(n, dtype=np.uint64) * ml).astype(np.uint64)
+        lens = np.full(n, ml, dtype=np.uint64)
+        self._engine = engine
+        self._h = ctypes.c_void_p()
+        engine.check(LIB.nw_sigset_create(engine.handle, ptrs.ctypes.data, lens.ctypes.data, slots.ctypes.data,
+                                          sigs.ctypes.data, n, ctypes.byref(self._h)), "nw_sigset_create")
+
+    @property
+    def handle(self):
+        return self._h
+
+    def __len__(self):
+        return LIB.nw_sigset_size(self._h)
+
+    def close(self):
+        if self._h:
+            LIB.nw_sigset_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class WorkerJob:
+    """One nw_worker_window_async submission in flight.  ``batches_used`` is known on return;
+    ``done()`` polls; ``wait()`` returns the window's nw_worker_result records as a structured numpy
+    array (``worker_result_dtype``), exactly once.  The frames and the set stay referenced by the job
+    until then, as the ABI requires."""
+
+    def __init__(self, engine: "Engine", frames, sigset: Optional[SigSet], zseed: Optional[bytes], batch_base: int = 0):
+        import numpy as np
+        self._engine = engine
+        self._sigset = sigset
+        self._frames = [DigestJob._as_bytes(f) for f in frames]
+        self.n = n = len(self._frames)
+        self._ptrs = np.array([f.ctypes.data if f.size else 0 for f in self._frames], np.uint64)
+        self._lens = np.array([f.size for f in self._frames], np.uint64)
+        self._out = np.zeros(max(n, 1), worker_result_dtype())
+        used = ctypes.c_uint64(0)
+        self._job = ctypes.c_void_p()
+        engine.check(LIB.nw_worker_window_async(engine.handle, sigset.handle if sigset is not None else None,
+                                                self._ptrs.ctypes.data, self._lens.ctypes.data, n,
+                                                _buf(bytes(zseed)) if zseed is not None else None, batch_base,
+                                                self._out.ctypes.data, ctypes.byref(used), ctypes.byref(self._job)),
+                     "nw_worker_window_async")
+        self.batches_used = used.value
+
+    def done(self) -> bool:
+        if not self._job:
+            return True
+        rc = LIB.nw_job_done(self._job)
+        if rc < 0 or rc > 1:
+            raise DeviceError("nw_job_done failed (rc=%d)" % rc)
+        return rc == 1
+
+    def wait(self):
+        if self._job:
+            job, self._job = self._job, ctypes.c_void_p()
+            self._engine.check(LIB.nw_job_wait(job), "nw_job_wait")
+            self._frames = None
+        return self._out[:self.n]
+
+    def __del__(self):
+        try:
+            if self._job:
+                LIB.nw_job_wait(self._job)   # a job must be waited for exactly once
+        except Exception:
+            pass
 
 
 class CoreJob:

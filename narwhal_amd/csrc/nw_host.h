@@ -4,6 +4,7 @@
 //   nw_staging.cpp    pinned staging (Stager, chunked uploads, message and signature uploads)
 //   nw_api.cpp        the three pipelines and the entry points
 //   nw_corepipe.cpp   the mixed Core batch: digests, both signature passes and the verdicts in one submission
+//   nw_workerpipe.cpp the worker window: digests and the verify load against a resident signature set in one job
 // The pure host arithmetic (layouts, plans) is nw_host_plan.h.
 //
 // Concurrency model (the worker calls from 64 rayon threads,
@@ -286,14 +287,15 @@ private:
 }  // namespace nw
 
 // An asynchronous host-buffer call in flight: its workspace lease, the caller's output and where the
-// result lands in the workspace's pinned buffer.  Two kinds, told apart only by what nw_job_wait
-// copies out: n x 64 digest bytes (nw_sha512_many_async) or n x 4 verdict bytes
-// (nw_core_batch_verify_async).  A job without a lease was complete when it was made.
+// result lands in the workspace's pinned buffer.  Three kinds, told apart only by what nw_job_wait
+// copies out: n x 64 digest bytes (nw_sha512_many_async), n x 4 verdict bytes
+// (nw_core_batch_verify_async) or n x 88 record bytes (nw_worker_window_async).  A job without a
+// lease was complete when it was made.
 struct nw_job {
     std::unique_ptr<nw::Lease> lease;
     uint8_t* out = nullptr;
     size_t n = 0;
-    size_t item = 64;    // bytes per result: 64 (digest) or 4 (verdict)
+    size_t item = 64;    // bytes per result: 64 (digest), 4 (verdict) or 88 (nw_worker_result)
     size_t o_out = 0;
     std::atomic<int>* inflight = nullptr;   // the context's async job count (released with the job)
     ~nw_job() {

@@ -430,6 +430,103 @@ inline DigestPack digest_pack(const size_t* len, size_t n) {
     return p;
 }
 
+// ------------------------------------------------------------------------------- worker windows
+// A window of serialized worker batches against a resident signature set (nw_worker_window_async,
+// nw_workerpipe.cpp).  A verifying frame verifies the set's first ``count`` signatures as
+// kWorkerChunks verify_batch chunks (worker/src/processor.rs:75-79); in the certificate pipeline a
+// chunk is one "certificate" over a range of VIRTUAL signatures: k_sigset_expand copies the frame's
+// count signatures out of the set to rows [vfirst, vfirst + count) of the run's flat arrays.
+constexpr uint32_t kWorkerChunks = 64;
+// Most virtual signatures of one run (one enqueue_certs call): 64 frames x 65,536, so a 64-frame
+// window of 62,500-transaction batches is one run.  It bounds the run's CertScratch and its expanded
+// arrays; a single frame above it is a run of its own.
+constexpr uint64_t kWorkerRunSigs = 4194304;
+
+// processor.rs:76-77: chunk c of count signatures covers [count*c/64, min(count, count*(c+1)/64)).
+// 64-bit throughout: count * 64 overflows 32 bits from 2^26 signatures.
+inline void worker_chunk(uint64_t count, uint32_t c, uint64_t* first, uint64_t* n) {
+    const uint64_t f = count * c / kWorkerChunks, e = std::min(count, count * (c + 1) / kWorkerChunks);
+    *first = f;
+    *n = e - f;
+}
+
+// (count, first virtual signature inside its run) of one verifying frame, as the kernels read it.
+struct WorkerFrame {
+    uint32_t count, vfirst;
+};
+// Frames [frame0, frame0 + nframes) of the window's verifying frames; chunk c of its frame k draws
+// its coefficients at batch index batch_base + 64 k + c.
+struct WorkerRun {
+    size_t frame0, nframes;
+    uint64_t nsigs, batch_base;
+};
+// The verifying frames of a window (count[j] <= the set's size, host-clamped) cut into runs at
+// frame boundaries, in order: a run is closed when the next frame would take it past kWorkerRunSigs.
+struct WorkerPlan {
+    std::vector<WorkerRun> runs;
+    std::vector<WorkerFrame> frames;
+    uint64_t total = 0, max_run_sigs = 0;
+    WorkerPlan(const uint32_t* count, size_t nv, uint64_t batch_base) : frames(nv) {
+        for (size_t j = 0; j < nv; ++j) {
+            if (runs.empty() || runs.back().nsigs + count[j] > kWorkerRunSigs)
+                runs.push_back(WorkerRun{j, 0, 0, batch_base + (uint64_t)kWorkerChunks * j});
+            WorkerRun& r = runs.back();
+            frames[j] = WorkerFrame{count[j], (uint32_t)r.nsigs};
+            r.nframes += 1;
+            r.nsigs += count[j];
+            total += count[j];
+            max_run_sigs = std::max(max_run_sigs, r.nsigs);
+        }
+    }
+    uint64_t batches_used() const { return (uint64_t)kWorkerChunks * frames.size(); }
+};
+
+// Host-decided part of one frame's result, 16 bytes: what k_worker_verdict passes through (n_tx,
+// status) and the frame's index among the verifying frames (kWorkerNoVerify: none).
+struct WorkerDesc {
+    int64_t n_tx;
+    uint32_t vindex;
+    int32_t status;
+};
+constexpr uint32_t kWorkerNoVerify = 0xFFFFFFFFu;
+constexpr size_t kWorkerResultBytes = 88;   // sizeof(nw_worker_result)
+
+// Device block of a worker window of nb frames (data_bytes packed at 16-byte aligned offsets), nv of
+// them verifying, the largest run of max_run_sigs virtual signatures:
+//   in    staged: the descriptor block (frame and verify descriptors, digest offsets and lengths) in
+//         one H2D, then the frames' bytes
+//   work  device only: the digests, the chunk verdict bytes and vote ranges of every verifying
+//         frame, and one run's expanded arrays (runs are serial in stream order and share them)
+//   out   the nb result records (one D2H)
+struct WorkerLayout {
+    Bump in, work, out;
+    size_t desc, vdesc, doff, dlen, data;
+    size_t dig, cok, first, nv, sig, signer, moff, mlen;
+    size_t result;
+    WorkerLayout(size_t nb, size_t nverify, size_t data_bytes, size_t max_run_sigs)
+        : desc(in.take(nb * sizeof(WorkerDesc))), vdesc(in.take(nverify * sizeof(WorkerFrame) + 8)),
+          doff(in.take(nb * 8)), dlen(in.take(nb * 8)), data(in.take(data_bytes + 16)), dig(work.take(nb * 64)),
+          cok(work.take(nverify * kWorkerChunks + 16)), first(work.take(nverify * kWorkerChunks * 4 + 16)),
+          nv(work.take(nverify * kWorkerChunks * 4 + 16)), sig(work.take(max_run_sigs * 64 + 16)),
+          signer(work.take(max_run_sigs * 4 + 16)), moff(work.take(max_run_sigs * 8 + 16)),
+          mlen(work.take(max_run_sigs * 8 + 16)), result(out.take(nb * kWorkerResultBytes)) {}
+    size_t head_bytes() const { return data; }             // the descriptor block: everything before the frames
+    size_t work_at() const { return in.end; }
+    size_t out_at() const { return in.end + work.end; }
+    size_t device_bytes() const { return in.end + work.end + out.end; }
+    size_t pinned_bytes() const { return std::max(in.end, out.end); }
+};
+
+// Device allocation of a resident signature set (nw_sigset): n signatures with ``total`` message bytes.
+struct SigSetLayout {
+    Bump b;
+    size_t sig, signer, moff, mlen, packed;
+    SigSetLayout(size_t n, size_t total)
+        : sig(b.take(n * 64 + 16)), signer(b.take(n * 4 + 4)), moff(b.take(n * 8 + 8)), mlen(b.take(n * 8 + 8)),
+          packed(b.take(total + 16)) {}
+    size_t bytes() const { return b.end; }
+};
+
 // Task plan of the segmented Pippenger MSM (nw_msm.hip) over nb consecutive batches (batch b = the
 // next counts[b] signatures).  Entries of batch b with first signature f: R entries [2f, 2f + c),
 // A entries [2f + c, 2f + 2c).  Windows below msm_nwin_r(C) cover both (z_i < 2^128 multiplies R),

@@ -753,4 +753,36 @@ int nw_core_batch_view(const nw_core_batch* b, size_t i, nw_core_view* out) {
     return NW_OK;
 }
 
+// The worker's frames (WorkerMessage, worker/src/worker.rs:37-40) with the same reader: what
+// bincode::deserialize at worker/src/processor.rs:68 accepts, and the transaction count :69-70 reads.
+// A count is checked against the bytes left BEFORE it drives a loop or a multiplication (every
+// transaction takes at least its 8 length bytes, every digest 32), and a length against the bytes
+// left before the position moves, so values up to 2^64 - 1 neither wrap nor allocate.
+int nw_worker_frame_count(const uint8_t* frame, size_t len, int64_t* n_tx) {
+    if (!n_tx || (len && !frame)) return NW_ERR_ARG;
+    *n_tx = -1;
+    Reader r{frame, len};
+    const uint32_t variant = r.u32();
+    const uint64_t n = r.u64();
+    if (!r.ok) return NW_ERR_ARG;   // truncated variant or count
+    if (variant == 0) {             // Batch(Vec<Transaction>), Transaction = Vec<u8>
+        if (n > (r.n - r.at) / 8) return NW_ERR_ARG;
+        for (uint64_t i = 0; i < n; ++i) {
+            const uint64_t ln = r.u64();
+            if (!r.ok || ln > r.n - r.at) return NW_ERR_ARG;
+            r.at += (size_t)ln;
+        }
+        *n_tx = (int64_t)n;
+        return NW_OK;
+    }
+    if (variant == 1) {             // BatchRequest(Vec<Digest>, PublicKey)
+        if (n > (r.n - r.at) / 32) return NW_ERR_ARG;
+        r.at += (size_t)n * 32;
+        Key requestor;
+        std::vector<uint8_t> scratch;
+        return r.public_key(requestor, scratch) ? NW_OK : NW_ERR_ARG;
+    }
+    return NW_ERR_ARG;              // unknown variant
+}
+
 }  // extern "C"

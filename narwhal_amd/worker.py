@@ -33,6 +33,11 @@ an idle MI355X: 190 GB of tables) and the second appends without a growth copy. 
 no committee (it verifies no committee signature).  Each batch's 64 chunks are ONE
 ``nw_verify_batches`` call on the cached comb tables.  Host logic only: every digest and verdict
 comes from libnwcrypto; there is no CPU hashing or verification in this module.
+
+``NativeProcessor`` is the same object on the native window call: the load's triples stay resident in
+HBM (``VerifyLoad.resident()``, nw_sigset_create) and one ``nw_worker_window_async`` job per window
+returns every batch's digest, transaction count, 64 chunk verdicts and status; frame parsing, the
+chunk split and the verify load are then the library's, not this module's.
 """
 from __future__ import annotations
 
@@ -141,6 +146,14 @@ class VerifyLoad:
         self.pks, self.sigs = engine.sign_many_np(seeds, self.msgs)
         self.slots = engine.committee_load_np(self.pks)
         self.verified = 0
+        self._resident = None
+
+    def resident(self):
+        """The load's triples as a ``SigSet`` resident in HBM (nw_sigset_create), made on first use and
+        kept: what ``NativeProcessor`` verifies against instead of re-uploading them per batch."""
+        if self._resident is None:
+            self._resident = self.engine.sigset(self.msgs, self.slots, self.sigs)
+        return self._resident
 
     def chunk_verdicts(self, count: int, zseed: bytes = None, batch_base: int = 0):
         """batch_ok[64] of the first ``count`` signatures split as processor.rs:75-79 does."""
@@ -280,3 +293,80 @@ class Processor:
             self.batcher.push(b)
             yield from self._deliver(self.batcher.ready())
         yield from self._deliver(self.batcher.drain())
+
+
+class NativeProcessor:
+    """``Processor`` on nw_worker_window_async: one asynchronous job per window of batches does the
+    digests (processor.rs:65) and, with ``verify`` (a ``VerifyLoad``), the simulated signature load
+    (:67-81) against the load's resident ``SigSet``; up to ``depth`` windows are in flight.
+
+    ``run(batches)`` stores and delivers in arrival order exactly like ``Processor(verify=...)``:
+    every batch before the first one that fails verification or does not deserialize is stored and
+    delivered; then ``VerificationPanic`` (NW_WORKER_VERIFY_FAILED) or ``ValueError``
+    (NW_WORKER_MALFORMED) is raised, and that batch is neither stored nor delivered.  Every window
+    draws a fresh 32-byte seed, and the NW-Z batch index is carried forward by each job's
+    ``batches_used``."""
+
+    def __init__(self, worker_id: int, own_digest: bool, store: Optional[MutableMapping] = None, engine=None,
+                 window: int = 64, depth: int = 2, verify: Optional[VerifyLoad] = None):
+        if window < 1 or depth < 1:
+            raise ValueError("window and depth must be >= 1")
+        self.id = worker_id
+        self.own_digest = own_digest
+        self.store = store if store is not None else {}
+        self.engine = engine or (verify.engine if verify is not None else _lib.default_engine())
+        self.window, self.depth = window, depth
+        self.verify = verify
+        self.batch_base = 0
+        self.submissions = 0
+        self._inflight: Deque[Tuple[List, object]] = deque()
+
+    def _submit(self, batches: List) -> None:
+        sigset = self.verify.resident() if self.verify is not None else None
+        zseed = os.urandom(32) if sigset is not None else None
+        job = self.engine.worker_window_submit(batches, sigset, zseed, self.batch_base)
+        self.batch_base += job.batches_used
+        self.submissions += 1
+        self._inflight.append((batches, job))
+
+    def _retire_oldest(self) -> Iterator[bytes]:
+        batches, job = self._inflight.popleft()
+        res = job.wait()
+        for b, digest, status, chunk_ok, verified, n_tx in zip(batches, res["digest"], res["status"].tolist(),
+                                                               res["chunk_ok"].tolist(), res["verified"].tolist(),
+                                                               res["n_tx"].tolist()):
+            if status == _lib.WORKER_MALFORMED:
+                raise ValueError("WorkerMessage: malformed batch")
+            if status != _lib.WORKER_OK:
+                raise VerificationPanic("verify_batch chunk(s) %s failed"
+                                        % [c for c in range(SIM_CHUNKS) if not (chunk_ok >> c) & 1])
+            if self.verify is not None:
+                if n_tx > self.verify.keys:
+                    warnings.warn("Batch size maximum for signature verification surpassed! %d" % n_tx)
+                self.verify.verified += verified
+            d = bytes(digest[:32])
+            self.store[d] = bytes(b)
+            yield serialize_worker_primary_message(d, self.id, self.own_digest)
+
+    def run(self, batches: Iterable) -> Iterator[bytes]:
+        open_window: List = []
+        try:
+            for b in batches:
+                open_window.append(b)
+                if len(open_window) >= self.window:
+                    while len(self._inflight) >= self.depth:   # bounded in-flight work: retire the oldest first
+                        yield from self._retire_oldest()
+                    self._submit(open_window)
+                    open_window = []
+                while self._inflight and self._inflight[0][1].done():
+                    yield from self._retire_oldest()
+            while open_window and len(self._inflight) >= self.depth:
+                yield from self._retire_oldest()
+            if open_window:
+                self._submit(open_window)
+            while self._inflight:
+                yield from self._retire_oldest()
+        finally:
+            # after a panic the later windows' results are dropped, but every job is still waited for
+            while self._inflight:
+                self._inflight.popleft()[1].wait()
