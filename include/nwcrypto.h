@@ -242,7 +242,7 @@ int nw_sha512_many_dev(nw_ctx* ctx, const uint8_t* d_base, const uint64_t* d_off
  * NW_ERR_NOMEM at once rather than blocking.  nw_job_done and nw_job_wait serve the Core jobs of
  * nw_core_batch_verify_async as well (nw_job_wait then fills n x 4 verdict bytes) and the worker
  * windows of nw_worker_window_async (n x 88 bytes), and the limit of 32 counts the jobs of all kinds
- * together. */
+ * together; so do the signing jobs of nw_sign_digests_async (n x 64) and nw_votes_make_async (n x 212). */
 typedef struct nw_job nw_job;
 int nw_sha512_many_async(nw_ctx* ctx, const uint8_t* const* msg, const size_t* len, size_t n,
                          uint8_t (*out)[64], nw_job** job);
@@ -256,6 +256,61 @@ int nw_sign_many(nw_ctx* ctx, const uint8_t (*seed)[32], const uint8_t* msgs, si
                  size_t n, uint8_t (*pk)[32], uint8_t (*sig)[64]);
 int nw_sign_many_dev(nw_ctx* ctx, const uint8_t* d_seed32, const uint8_t* d_msgs, size_t msg_len,
                      size_t n, uint8_t* d_pk32, uint8_t* d_sig64, void* stream);
+
+/* ---- signing with a resident key: batched signatures and Vote frames out ------------------------
+ * The reply half of Core: for every header it accepts, Core::process_header answers with a vote
+ * (primary/src/core.rs:184-206): Vote::new (primary/src/messages.rs:113-129: one SHA-512 of 72 bytes
+ * and one Signature::new through the SignatureService, crypto/src/lib.rs:229-249), then
+ * bincode::serialize(&PrimaryMessage::Vote(..)).  A signer holds ONE key on the device; a call signs
+ * n messages with it in one submission (one upload, one kernel, one download).  nw_sign_many above
+ * takes a seed per signature and re-derives the key in every lane; it stays as it is.
+ *
+ * nw_signer_create: seed = the first 32 bytes of the reference's 64-byte SecretKey.  One small kernel
+ * expands it on the device (the library has no host SHA-512) into a record of a mod l, the 32-byte
+ * nonce prefix, the compressed public key A and A's base64 string; the staging bytes that held the
+ * seed, pinned and device, are overwritten before the call returns.  nw_signer_public: A.
+ * nw_signer_destroy waits for every pending call of the context (as nw_committee_load does before it
+ * changes the key cache), zeroes the record on the device, then frees it.  nw_ctx_destroy does the same
+ * to the record of every signer still alive; such a signer is then good for nw_signer_public and
+ * nw_signer_destroy only (every other call with it is NW_ERR_ARG).  A signer reads the basepoint table under the shared key lock, as nw_sign_many_dev
+ * does, and never touches the key cache.
+ *
+ * Threat model: the key lives in HBM, in the clear, for the life of the signer.  As in nw_sign_many,
+ * the basepoint comb's table gathers are indexed by digits of the secret nonce and are not
+ * constant-time (the one field inversion per wave is: fixed-iteration divsteps).  The signer is for a
+ * GPU the node owns and shares with nobody.
+ *
+ * nw_sign_digests: SignatureService::request_signature for n 32-byte digests: sig[i] = the RFC 8032
+ * signature of digest[i], bit for bit what nw_sign_many gives for (seed, digest[i]).
+ * nw_votes_make: core.rs:192 + :204 for n accepted headers.  req[i] = header id (32) || round (u64
+ * LE) || header author (32), which is exactly Hash for Vote's preimage (messages.rs:145-153);
+ * frame[i] = the 212 bytes of bincode::serialize(&PrimaryMessage::Vote(Vote::new(..))) with the
+ * signer as the vote's author:
+ *     0 u32 1 | 4 id | 36 round | 44 u64 44 | 52 origin base64 | 96 u64 44 | 104 author base64 |
+ *     148 signature part1 | 180 part2
+ *
+ * The _async forms enqueue the same submission and return a job: nw_job_done polls, nw_job_wait
+ * fills sig (n x 64) / frame (n x 212) and frees the job.  digest / req may be freed on return; sig /
+ * frame must live until the wait.  The jobs count against the 32 unwaited jobs of a context; an
+ * nw_committee_load that changes the key cache, and nw_signer_destroy, wait for them on the device.
+ *
+ * NW_ERR_ARG: NULL ctx, signer, out or job; a NULL array with n > 0; a signer of another context;
+ * n above 2^24.  n == 0 is NW_OK with nothing launched (the job form yields a job that is complete). */
+typedef struct nw_signer nw_signer;
+int nw_signer_create(nw_ctx* ctx, const uint8_t seed[32], nw_signer** out);
+int nw_signer_public(const nw_signer* signer, uint8_t pk[32]);
+void nw_signer_destroy(nw_signer* signer);
+
+int nw_sign_digests(nw_ctx* ctx, const nw_signer* signer, const uint8_t (*digest)[32], size_t n, uint8_t (*sig)[64]);
+int nw_sign_digests_async(nw_ctx* ctx, const nw_signer* signer, const uint8_t (*digest)[32], size_t n,
+                          uint8_t (*sig)[64], nw_job** job);
+
+#define NW_VOTE_REQ_BYTES 72
+#define NW_VOTE_FRAME_BYTES 212
+int nw_votes_make(nw_ctx* ctx, const nw_signer* signer, const uint8_t (*req)[NW_VOTE_REQ_BYTES], size_t n,
+                  uint8_t (*frame)[NW_VOTE_FRAME_BYTES]);
+int nw_votes_make_async(nw_ctx* ctx, const nw_signer* signer, const uint8_t (*req)[NW_VOTE_REQ_BYTES], size_t n,
+                        uint8_t (*frame)[NW_VOTE_FRAME_BYTES], nw_job** job);
 
 /* ---- measurement --------------------------------------------------------------------------
  * When enabled, HIP events are recorded on the launch stream around every k_verify launch; read

@@ -96,7 +96,9 @@ _OPTIONAL = {"nw_abi_version", "nw_profile_read_sigs", "nw_base_window", "nw_cer
              "nw_core_batch_verify_async", "nw_core_messages_verify_async", "nw_core_agg_create",
              "nw_core_agg_destroy", "nw_core_agg_set_header", "nw_core_agg_advance_gc", "nw_core_agg_state",
              "nw_core_agg_apply", "nw_core_agg_refs", "nw_sigset_create", "nw_sigset_size", "nw_sigset_destroy",
-             "nw_worker_frame_count", "nw_worker_window_async", "nw_worker_window"}
+             "nw_worker_frame_count", "nw_worker_window_async", "nw_worker_window", "nw_signer_create",
+             "nw_signer_public", "nw_signer_destroy", "nw_sign_digests", "nw_sign_digests_async", "nw_votes_make",
+             "nw_votes_make_async"}
 
 WORKER_OK, WORKER_VERIFY_FAILED, WORKER_MALFORMED = 0, 1, 2   # NW_WORKER_* (nw_worker_result.status)
 WORKER_CHUNKS = 64                                            # verify_batch chunks per batch
@@ -174,6 +176,13 @@ def _load() -> ctypes.CDLL:
         "nw_worker_frame_count": (I, [P, S, ctypes.POINTER(ctypes.c_int64)]),
         "nw_worker_window_async": (I, [P, P, P, P, S, P, U64, P, ctypes.POINTER(U64), ctypes.POINTER(P)]),
         "nw_worker_window": (I, [P, P, P, P, S, P, U64, P, ctypes.POINTER(U64)]),
+        "nw_signer_create": (I, [P, P, ctypes.POINTER(P)]),
+        "nw_signer_public": (I, [P, P]),
+        "nw_signer_destroy": (None, [P]),
+        "nw_sign_digests": (I, [P, P, P, S, P]),
+        "nw_sign_digests_async": (I, [P, P, P, S, P, ctypes.POINTER(P)]),
+        "nw_votes_make": (I, [P, P, P, S, P]),
+        "nw_votes_make_async": (I, [P, P, P, S, P, ctypes.POINTER(P)]),
     }
     for name, (res, args) in sig.items():
         if name in _OPTIONAL and not hasattr(lib, name):
@@ -212,6 +221,7 @@ class Engine:
         if rc != NW_OK:
             raise DeviceError("nw_ctx_create failed (rc=%d): no usable gfx950 GPU" % rc)
         self.device = device
+        self._signers = []   # weak references to this engine's live Signers (closed with it)
 
     # -- plumbing -----------------------------------------------------------------------------
     @property
@@ -220,6 +230,11 @@ class Engine:
 
     def close(self):
         if self._ctx:
+            for ref in self._signers:   # before the context goes: their handles hold it
+                s = ref()
+                if s is not None:
+                    s.close()
+            self._signers = []
             LIB.nw_ctx_destroy(self._ctx)
             self._ctx = ctypes.c_void_p()
 
@@ -390,6 +405,11 @@ class Engine:
                                     mlen, n, pk, sg), "nw_sign_many")
         return ([pk.raw[32 * i:32 * i + 32] for i in range(n)], [sg.raw[64 * i:64 * i + 64] for i in range(n)])
 
+
+    def signer(self, seed: bytes) -> "Signer":
+        """nw_signer_create: keep one key resident on the GPU (``seed``: the first 32 bytes of the
+        reference's SecretKey) for batched signatures and signed Vote frames."""
+        return Signer(self, seed)
 
     # -- numpy bulk paths (large synthetic workloads) -------------------------------------------
     def sign_many_np(self, seeds, msgs):
@@ -683,6 +703,138 @@ class SigSet:
     def __del__(self):
         try:
             self.close()
+        except Exception:
+            pass
+
+
+VOTE_REQ_BYTES, VOTE_FRAME_BYTES = 72, 212   # NW_VOTE_REQ_BYTES, NW_VOTE_FRAME_BYTES
+
+
+def vote_request(header_id: bytes, round_: int, header_author: bytes) -> bytes:
+    """The 72-byte request of nw_votes_make for one accepted header: Hash for Vote's preimage."""
+    req = bytes(header_id) + int(round_).to_bytes(8, "little") + bytes(header_author)
+    if len(req) != VOTE_REQ_BYTES:
+        raise ValueError("vote request: a 32-byte header id and a 32-byte author")
+    return req
+
+
+class Signer:
+    """nw_signer: one secret key expanded and resident on the GPU.  ``sign_digests`` is
+    SignatureService::request_signature for many 32-byte digests in one submission; ``make_votes``
+    turns (header id, round, header author) requests into the serialized ``PrimaryMessage::Vote``
+    replies of Core::process_header, signed by this key, in one submission.  The ``*_async`` forms
+    return a ``SignJob``.  ``Engine.close`` closes the engine's signers first; a closed signer raises on use."""
+
+    def __init__(self, engine: "Engine", seed: bytes):
+        seed = bytes(seed)
+        if len(seed) != 32:
+            raise ValueError("Signer: the seed is the first 32 bytes of the SecretKey")
+        self._engine = engine
+        self._h = ctypes.c_void_p()
+        engine.check(LIB.nw_signer_create(engine.handle, _buf(seed), ctypes.byref(self._h)), "nw_signer_create")
+        pk = ctypes.create_string_buffer(32)
+        engine.check(LIB.nw_signer_public(self._h, pk), "nw_signer_public")
+        self.public = pk.raw
+        import weakref
+        engine._signers = [r for r in engine._signers if r() is not None] + [weakref.ref(self)]
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def closed(self) -> bool:
+        return not self._h
+
+    @staticmethod
+    def _items(items, size: int, what: str):
+        """uint8[N, size] from a list of bytes-like objects or an array."""
+        import numpy as np
+        if isinstance(items, np.ndarray):
+            a = np.ascontiguousarray(items, dtype=np.uint8)
+        else:
+            items = [bytes(x) for x in items]
+            if any(len(x) != size for x in items):
+                raise ValueError("%s: every item is %d bytes" % (what, size))
+            a = np.frombuffer(b"".join(items), np.uint8).reshape(len(items), size)
+        if a.ndim != 2 or a.shape[1] != size:
+            raise ValueError("%s: every item is %d bytes" % (what, size))
+        return a
+
+    def _call(self, fn, name: str, items, in_size: int, out_size: int, as_array: bool):
+        import numpy as np
+        if not self._h:
+            raise DeviceError("%s: the signer is closed" % name)
+        a = self._items(items, in_size, name)
+        n = a.shape[0]
+        out = np.zeros((max(n, 1), out_size), np.uint8)
+        self._engine.check(fn(self._engine.handle, self._h, a.ctypes.data if n else None, n,
+                              out.ctypes.data if n else None), name)
+        return out[:n] if as_array else [out[i].tobytes() for i in range(n)]
+
+    def sign_digests(self, digests, as_array: bool = False):
+        """nw_sign_digests: the 64-byte signatures of 32-byte digests (a list of bytes, or with
+        ``as_array`` uint8[N, 64])."""
+        return self._call(LIB.nw_sign_digests, "nw_sign_digests", digests, 32, 64, as_array)
+
+    def make_votes(self, reqs, as_array: bool = False):
+        """nw_votes_make: the 212-byte vote frames of 72-byte requests (``vote_request``)."""
+        return self._call(LIB.nw_votes_make, "nw_votes_make", reqs, VOTE_REQ_BYTES, VOTE_FRAME_BYTES, as_array)
+
+    def sign_digests_async(self, digests) -> "SignJob":
+        return SignJob(self, LIB.nw_sign_digests_async, "nw_sign_digests_async", self._items(digests, 32, "digests"), 64)
+
+    def make_votes_async(self, reqs) -> "SignJob":
+        return SignJob(self, LIB.nw_votes_make_async, "nw_votes_make_async",
+                       self._items(reqs, VOTE_REQ_BYTES, "requests"), VOTE_FRAME_BYTES)
+
+    def close(self):
+        if self._h:
+            LIB.nw_signer_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SignJob:
+    """One nw_sign_digests_async / nw_votes_make_async submission in flight.  ``done()`` polls;
+    ``wait()`` returns the signatures or frames in submission order (waits exactly once).  The inputs
+    are staged at submit; the output buffer lives in the job."""
+
+    def __init__(self, signer: Signer, fn, name: str, items, out_size: int):
+        import numpy as np
+        if signer.closed:
+            raise DeviceError("%s: the signer is closed" % name)
+        self._engine = signer._engine
+        self._signer = signer
+        self.n = n = items.shape[0]
+        self._out = np.zeros((max(n, 1), out_size), np.uint8)
+        self._job = ctypes.c_void_p()
+        self._engine.check(fn(self._engine.handle, signer.handle, items.ctypes.data if n else None, n,
+                              self._out.ctypes.data if n else None, ctypes.byref(self._job)), name)
+
+    def done(self) -> bool:
+        if not self._job:
+            return True
+        rc = LIB.nw_job_done(self._job)
+        if rc < 0 or rc > 1:
+            raise DeviceError("nw_job_done failed (rc=%d)" % rc)
+        return rc == 1
+
+    def wait(self) -> list:
+        if self._job:
+            job, self._job = self._job, ctypes.c_void_p()
+            self._engine.check(LIB.nw_job_wait(job), "nw_job_wait")
+        return [self._out[i].tobytes() for i in range(self.n)]
+
+    def __del__(self):
+        try:
+            if self._job:
+                LIB.nw_job_wait(self._job)   # a job must be waited for exactly once
         except Exception:
             pass
 

@@ -84,6 +84,38 @@ class CertificatesAggregator:
         return None
 
 
+class Voter:
+    """The reply half of ``Core::process_header`` (primary/src/core.rs:184-212): at most one vote per
+    (round, header author) (``last_voted``, :184-190), each vote a ``Vote::new`` signed with the
+    node's key and serialized as ``PrimaryMessage::Vote`` (:192, :204).  ``signer`` is the node's
+    resident key (``Engine.signer`` / ``SignatureService.signer``; anything with ``make_votes`` and
+    ``public``).  ``votes_for(headers)`` takes the headers a batch accepted, in arrival order, and
+    returns one (header author, frame) pair per header that gets a vote: where to send, and the bytes
+    to send, all from ONE ``make_votes`` call.  The parent and payload checks that precede the vote
+    in the reference (:150-178) belong to the synchronizer and are out of scope."""
+
+    def __init__(self, signer):
+        self.signer = signer
+        self.name = bytes(signer.public)
+        self.last_voted: Dict[int, set] = {}
+
+    def votes_for(self, headers: Sequence[Header]) -> List[Tuple[bytes, bytes]]:
+        pick = []
+        for h in headers:
+            seen = self.last_voted.setdefault(h.round, set())
+            if h.author not in seen:                                  # HashSet::insert is true: vote
+                seen.add(h.author)
+                pick.append(h)
+        if not pick:
+            return []
+        frames = self.signer.make_votes([_lib.vote_request(h.id, h.round, h.author) for h in pick])
+        return [(h.author, f) for h, f in zip(pick, frames)]
+
+    def cleanup(self, gc_round: int) -> None:
+        """core.rs:404: ``last_voted.retain(|k, _| k >= &gc_round)``."""
+        self.last_voted = {r: a for r, a in self.last_voted.items() if r >= gc_round}
+
+
 def state_error(m, gc_round: int, current_header: Header) -> Optional[DagError]:
     """The checks of ``Core::sanitize_*`` that read Core's mutable state (gc_round, the current
     header), in the reference's order; they run before any signature check."""
@@ -238,9 +270,16 @@ class CoreBatcher:
     ``submit_frames_native(frames)`` and ``pipeline_frames(batches)`` are the same two on wire frames
     with nothing but the hand-off in Python: asynchronous native jobs (nw_core_batch_verify_async),
     then the native aggregators (nw_core_agg_apply) for the state checks, the votes and the
-    certificates."""
+    certificates.
 
-    def __init__(self, committee: Committee, engine=None, gc_depth: int = 50, device_votes: bool = False):
+    With a ``voter`` (``Voter``) every batch's accepted headers are answered: the (header author,
+    vote frame) pairs of each applied batch are appended to ``sent_votes``, one ``make_votes``
+    submission per batch.  What the methods return is the same with and without."""
+
+    def __init__(self, committee: Committee, engine=None, gc_depth: int = 50, device_votes: bool = False,
+                 voter: Optional[Voter] = None):
+        self.voter = voter
+        self.sent_votes: List[Tuple[bytes, bytes]] = []
         self.committee = committee
         self.device_votes = device_votes   # submit_frames: certificate votes decoded on the GPU
         self.engine = engine or _lib.default_engine()
@@ -290,6 +329,9 @@ class CoreBatcher:
             elif err is None and isinstance(m, Certificate):
                 self._process_certificate(m, parents)
             errs.append(err)
+        if self.voter is not None:
+            self.sent_votes.extend(self.voter.votes_for(
+                [m for m, e in zip(messages, errs) if e is None and isinstance(m, Header)]))
         return errs, assembled, parents
 
     def submit(self, messages: Sequence, zseed: Optional[bytes] = None):
@@ -360,6 +402,8 @@ class CoreBatcher:
             self.gc_round = consensus_round - self.gc_depth
             self.certificates_aggregators = {r: a for r, a in self.certificates_aggregators.items()
                                              if r >= self.gc_round}
+            if self.voter is not None:
+                self.voter.cleanup(self.gc_round)
         if self._agg is not None:
             self._agg.advance_gc(consensus_round)
             for key in [k for k, c in self._held_certs.items() if self._held_round(c) < self.gc_round]:
@@ -414,6 +458,10 @@ class CoreBatcher:
             else:
                 got = [self._held_certs.pop((t, i, "assembled") if a else (t, i)) for t, i, a in refs]
                 parents.append(([c if isinstance(c, Certificate) else decode_primary_message(c) for c in got], round_))
+        if self.voter is not None:   # variant 0: Header
+            self.sent_votes.extend(self.voter.votes_for(
+                [decode_primary_message(f) for f, c in zip(frames, codes)
+                 if c == _lib.DAG_OK and len(f) >= 4 and f[:4] == b"\0\0\0\0"]))
         return _errors(codes), assembled, parents
 
     @staticmethod

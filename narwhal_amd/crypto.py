@@ -16,7 +16,7 @@ reference (crypto/src/lib.rs)              here
 ``Signature::new`` (:185-191)              ``Signature.new`` (GPU signing kernel)
 ``Signature::verify`` (:200-204)           ``Signature.verify`` -> strict verify on the GPU
 ``Signature::verify_batch`` (:206-219)     ``Signature.verify_batch`` -> batch verify on the GPU
-``SignatureService`` (:222-250)            ``SignatureService``
+``SignatureService`` (:222-250)            ``SignatureService`` (+ ``request_signatures``: batched)
 =========================================  ==============================================
 
 ``verify``/``verify_batch`` return None on success and raise ``CryptoError`` on failure
@@ -229,6 +229,7 @@ class SignatureService:
 
     def __init__(self, secret: SecretKey):
         self._secret = secret
+        self._signers = {}   # id(engine) -> (engine, its Signer)
 
     async def request_signature(self, digest: Digest) -> Signature:
         loop = asyncio.get_running_loop()
@@ -236,6 +237,20 @@ class SignatureService:
 
     def request_signature_sync(self, digest: Digest) -> Signature:
         return Signature.new(digest, self._secret)
+
+    def signer(self, engine=None):
+        """The service's key resident on ``engine`` (nw_signer): created on first use, one per engine."""
+        eng = engine or _engine()
+        hit = self._signers.get(id(eng))
+        if hit is None or hit[0] is not eng or hit[1].closed:   # a closed signer is replaced
+            hit = self._signers[id(eng)] = (eng, eng.signer(self._secret.seed))
+        return hit[1]
+
+    def request_signatures(self, digests: Iterable[Digest], engine=None) -> list:
+        """``request_signature`` for many digests: one GPU submission with the resident key
+        (nw_sign_digests) instead of one task round trip per digest (crypto/src/lib.rs:229-249)."""
+        sigs = self.signer(engine).sign_digests([bytes(d) for d in digests])
+        return [Signature.from_bytes(s) for s in sigs]
 
 
 def sha512(data: bytes) -> bytes:

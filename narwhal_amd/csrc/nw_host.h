@@ -5,6 +5,7 @@
 //   nw_api.cpp        the three pipelines and the entry points
 //   nw_corepipe.cpp   the mixed Core batch: digests, both signature passes and the verdicts in one submission
 //   nw_workerpipe.cpp the worker window: digests and the verify load against a resident signature set in one job
+//   nw_signpipe.cpp   signing with a resident key: signatures or signed Vote frames in one submission
 // The pure host arithmetic (layouts, plans) is nw_host_plan.h.
 //
 // Concurrency model (the worker calls from 64 rayon threads,
@@ -197,6 +198,9 @@ struct nw_ctx {
     std::vector<std::unique_ptr<nw::Workspace>> pool;
     std::vector<nw::Workspace*> free_ws;
     std::atomic<int> async_jobs{0};   // unwaited asynchronous jobs of both kinds (<= kMaxAsyncJobs)
+    // live signers (nw_signpipe.cpp): nw_ctx_destroy zeroes and frees the key records of those still alive
+    std::mutex signers_mu;
+    std::vector<struct nw_signer*> signers;
     // measurement: (start, stop) event pairs around k_verify launches
     std::mutex prof_mu;
     bool prof_on = false;
@@ -287,15 +291,16 @@ private:
 }  // namespace nw
 
 // An asynchronous host-buffer call in flight: its workspace lease, the caller's output and where the
-// result lands in the workspace's pinned buffer.  Three kinds, told apart only by what nw_job_wait
+// result lands in the workspace's pinned buffer.  Four kinds, told apart only by what nw_job_wait
 // copies out: n x 64 digest bytes (nw_sha512_many_async), n x 4 verdict bytes
-// (nw_core_batch_verify_async) or n x 88 record bytes (nw_worker_window_async).  A job without a
-// lease was complete when it was made.
+// (nw_core_batch_verify_async), n x 88 record bytes (nw_worker_window_async) or n x 64 signature /
+// n x 212 vote-frame bytes (nw_sign_digests_async / nw_votes_make_async).  A job without a lease was
+// complete when it was made.
 struct nw_job {
     std::unique_ptr<nw::Lease> lease;
     uint8_t* out = nullptr;
     size_t n = 0;
-    size_t item = 64;    // bytes per result: 64 (digest), 4 (verdict) or 88 (nw_worker_result)
+    size_t item = 64;    // bytes per result: 64 (digest, signature), 4 (verdict), 88 (nw_worker_result), 212 (vote frame)
     size_t o_out = 0;
     std::atomic<int>* inflight = nullptr;   // the context's async job count (released with the job)
     ~nw_job() {
@@ -343,6 +348,9 @@ int enqueue_certs(nw_ctx* ctx, Workspace* ws, const CertCall& c, const CertPlan&
 
 // Wait for every call that may still read the key tables (exclusive key lock held).
 int drain_all(nw_ctx* ctx);
+// nw_ctx_destroy, with every stream idle: zero and free the key record of every signer still alive
+// and detach it from the context (its nw_signer_destroy then only frees the handle).
+void release_signers(nw_ctx* ctx);
 
 // Key cache (nw_keycache.cpp).  Slots of keys already in the cache (shared lock held): true when
 // every key is cached.

@@ -430,6 +430,23 @@ inline DigestPack digest_pack(const size_t* len, size_t n) {
     return p;
 }
 
+// Blocks of a signing call with a resident key (nw_sign_digests / nw_votes_make, nw_signpipe.cpp):
+// n inputs of in_item bytes (32: digests, 72: vote requests) go up in one H2D, n outputs of out_item
+// bytes (64: signatures, 212: vote frames) come back in one D2H.  In the device block the outputs
+// lie behind the inputs; in the pinned block they land on its front, over the staged inputs, once
+// the one H2D has read them (stream order, as for the Core batch's verdicts).
+struct SignLayout {
+    Bump b;
+    size_t in, out;   // device offsets
+    size_t in_bytes, out_bytes;
+    SignLayout(size_t n, size_t in_item, size_t out_item)
+        : in(b.take(n * in_item)), out(b.take(n * out_item)), in_bytes(n * in_item), out_bytes(n * out_item) {}
+    size_t device_bytes() const { return b.end; }
+    size_t pinned_bytes() const { return align256(std::max(in_bytes, out_bytes)); }
+};
+// Signatures per signing call (the kernel indexes in 32 bits: 2^24 frames are 3.6 GB)
+constexpr size_t kSignMaxItems = (size_t)1 << 24;
+
 // ------------------------------------------------------------------------------- worker windows
 // A window of serialized worker batches against a resident signature set (nw_worker_window_async,
 // nw_workerpipe.cpp).  A verifying frame verifies the set's first ``count`` signatures as

@@ -180,5 +180,11 @@ hipError_t launch_sha512_many(uint32_t n, const uint8_t* base, const uint64_t* o
                               uint8_t* out, hipStream_t st);
 hipError_t launch_sign(uint32_t n, int msg_words, const uint32_t* seeds, const uint32_t* msgs,
                        const uint32_t* btab, uint32_t* pk, uint32_t* sig, hipStream_t st);
+// Signing with a resident key (nw_sign.hip, nw_signkey.h).  k_signer_expand: the 32-byte seed at
+// ``seed`` -> the signer record (SIGNER_REC_WORDS words).  k_sign_key<mode>: n digests (mode 0:
+// [n][32] -> [n][64] signatures) or n vote requests (mode 1: [n][72] -> [n][212] frames).
+hipError_t launch_signer_expand(const uint32_t* seed, const uint32_t* btab, uint32_t* rec, hipStream_t st);
+hipError_t launch_sign_key(int mode, uint32_t n, const uint32_t* rec, const uint32_t* in, const uint32_t* btab,
+                           uint32_t* out, hipStream_t st);
 
 }  // namespace nw

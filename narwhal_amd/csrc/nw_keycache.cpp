@@ -305,6 +305,7 @@ void nw_ctx_destroy(nw_ctx* ctx) {
         if (w->pending) (void)hipEventSynchronize(w->done);
         if (w->stream) (void)hipStreamSynchronize(w->stream);
     }
+    release_signers(ctx);   // key records of signers the caller has not destroyed: zeroed, freed
     ctx->free_ws.clear();
     ctx->pool.clear();   // the buffers, events and streams of every workspace
     ctx->w_bases.release();

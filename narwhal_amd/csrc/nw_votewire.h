@@ -1,6 +1,8 @@
 // The wire record of one certificate vote, and the one decoder of its key that both the host tests
 // and the device (k_votes_ingest, nw_votes.hip) use.  Plain C++: compiles under g++ (nw_primary.cpp
 // is built without HIP) and as device code; NW_VW_HD is this header's own host/device macro.
+// Further down, the other direction: the key encoder and the writer of the vote frame a node sends
+// (k_sign_key<1>, nw_sign.hip).
 //
 //   record:  u64 len (LE) | len bytes of base64 string | 64-byte signature
 //   regular: len == 44 in every vote of a certificate, and all of them inside the frame; vote v of
@@ -86,6 +88,69 @@ NW_VW_HD bool vw_key_decode(const uint8_t s[44], uint8_t key[32]) {
     const bool ok = vw_key_decode_words(w, k);
     for (int i = 0; i < 32; ++i) key[i] = (uint8_t)(k[i >> 2] >> (8 * (i & 3)));
     return ok;
+}
+
+// ---- the other direction: the vote a node SENDS (nw_votes_make, k_sign_key<1> in nw_sign.hip) ----
+// bincode of PrimaryMessage::Vote(vote), fixed at 212 bytes = 53 dwords:
+//   0 u32 tag 1 | 4 header id | 36 round u64 | 44 u64 44 | 52 origin, base64 | 96 u64 44 |
+//   104 author, base64 | 148 signature part1 | 180 signature part2
+// The request a frame is made from is Hash for Vote's preimage (primary/src/messages.rs:145-153):
+//   header id (32) | round u64 LE | header author (32) = 72 bytes = 18 dwords.
+// Frames lie back to back, so every field of every frame is 4-byte aligned.
+constexpr uint32_t kVoteReqBytes = 72, kVoteReqWords = kVoteReqBytes / 4;
+constexpr uint32_t kVoteFrameBytes = 4 + 32 + 8 + 2 * (8 + kVoteKeyChars) + 64;   // 212
+constexpr uint32_t kVoteFrameWords = kVoteFrameBytes / 4;                        // 53
+constexpr uint32_t kVoteKeyStrWords = kVoteKeyChars / 4;                         // 11
+// dword offsets inside a frame
+constexpr uint32_t kVfTag = 0, kVfId = 1, kVfRound = 9, kVfOriginLen = 11, kVfOrigin = 13, kVfAuthorLen = 24,
+                   kVfAuthor = 26, kVfSig = 37;
+static_assert(kVoteFrameBytes == 212 && kVoteFrameWords * 4 == kVoteFrameBytes, "vote frame");
+static_assert(kVfSig + 16 == kVoteFrameWords && kVfAuthor + kVoteKeyStrWords == kVfSig, "vote frame fields");
+
+// Character of a base64 symbol 0..63 (the STANDARD alphabet), without a table.
+NW_VW_HD uint32_t vw_char(uint32_t v) {
+    return v < 26 ? 'A' + v : v < 52 ? 'a' + (v - 26) : v < 62 ? '0' + (v - 52) : v == 62 ? '+' : '/';
+}
+
+// The inverse of vw_key_decode_words: the key's 8 little-endian dwords to the 44 characters of its
+// canonical padded base64 string (PublicKey::encode_base64), as 11 little-endian dwords.
+NW_VW_HD void vw_key_encode_words(const uint32_t key[8], uint32_t s[11]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int q = 0; q < 11; ++q) {
+        uint32_t t = 0;   // bytes 3q, 3q + 1, 3q + 2 of the key, big end first (byte 32 does not exist)
+        for (int j = 0; j < 3; ++j) {
+            const int at = 3 * q + j;
+            if (at < 32) t |= ((key[at >> 2] >> (8 * (at & 3))) & 0xFF) << (16 - 8 * j);
+        }
+        const uint32_t c3 = q == 10 ? (uint32_t)'=' : vw_char(t & 63);
+        s[q] = vw_char(t >> 18) | vw_char((t >> 12) & 63) << 8 | vw_char((t >> 6) & 63) << 16 | c3 << 24;
+    }
+}
+
+// The same on bytes (host tests; any alignment).
+NW_VW_HD void vw_key_encode(const uint8_t key[32], uint8_t s[44]) {
+    uint32_t k[8], w[11];
+    for (int q = 0; q < 8; ++q)
+        k[q] = (uint32_t)key[4 * q] | (uint32_t)key[4 * q + 1] << 8 | (uint32_t)key[4 * q + 2] << 16 | (uint32_t)key[4 * q + 3] << 24;
+    vw_key_encode_words(k, w);
+    for (int i = 0; i < 44; ++i) s[i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
+}
+
+// One vote frame from its request, the author's key string (encoded once per signer) and the
+// signature; the origin's string is encoded here.  frame: 53 dwords.
+NW_VW_HD void vw_vote_frame_words(const uint32_t req[18], const uint32_t author_str[11], const uint32_t sig[16],
+                                  uint32_t frame[53]) {
+    frame[kVfTag] = 1;   // PrimaryMessage::Vote
+    for (int k = 0; k < 10; ++k) frame[kVfId + k] = req[k];   // header id, round
+    frame[kVfOriginLen] = kVoteKeyChars;
+    frame[kVfOriginLen + 1] = 0;
+    vw_key_encode_words(req + 10, frame + kVfOrigin);
+    frame[kVfAuthorLen] = kVoteKeyChars;
+    frame[kVfAuthorLen + 1] = 0;
+    for (int k = 0; k < 11; ++k) frame[kVfAuthor + k] = author_str[k];
+    for (int k = 0; k < 16; ++k) frame[kVfSig + k] = sig[k];
 }
 
 // Hash of a committee name into the device committee index's open-addressing table (names are

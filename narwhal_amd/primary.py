@@ -225,6 +225,26 @@ class Vote:
     def digest(self, engine=None) -> bytes:
         return (engine or _lib.default_engine()).sha512(self.digest_preimage())[:32]
 
+    @classmethod
+    def new(cls, header: "Header", author: bytes, service, engine=None) -> "Vote":
+        """Vote::new (:113-129): our vote for ``header``, signed through the SignatureService."""
+        from .crypto import Digest
+        v = cls(header.id, header.round, header.author, author)
+        v.signature = service.request_signature_sync(Digest(v.digest(engine))).flatten()
+        return v
+
+    @classmethod
+    def new_many(cls, headers: Sequence["Header"], author: bytes, service, engine=None) -> List["Vote"]:
+        """``Vote.new`` for many headers in ONE GPU submission: the service's resident key hashes,
+        signs and serializes every vote on the device (nw_votes_make); the votes are read back from
+        the frames."""
+        reqs = [_lib.vote_request(h.id, h.round, h.author) for h in headers]
+        frames = service.signer(engine).make_votes(reqs)
+        votes = [decode_primary_message(f) for f in frames]
+        if any(v.author != bytes(author) for v in votes):
+            raise ValueError("Vote.new_many: the service's key is not ``author``")
+        return votes
+
     def to_bytes(self) -> bytes:
         return self.id + struct.pack("<Q", self.round) + _pk_bytes(self.origin) + _pk_bytes(self.author) + self.signature
 
